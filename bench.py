@@ -14,6 +14,12 @@ Multi-GPU: `torch.distributed.run --nproc-per-node N bench.py --gpus N`: each ra
 same snapshot on its GPU and checks its own batch (weak scaling, no data-path collective;
 SURVEY.md 8e "replicas").  Timing: barrier + synchronize on both sides of exactly K steps, max
 over ranks; rank 0 prints ONE JSON line.
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) builds the graph, warms up, times the K steps
+and prints the headline's line.  `--full` adds, after the timed steps, everything else the line can
+carry: the tail tier's roofline phase, the latency phase, the host-path leg, parity against the oracle,
+the CPU baseline and the C5 / C3 / heavy-tail / sharded sub-lines.  `--dump-outputs DIR` writes the
+last timed step's answers and error codes as DIR/allowed.npy and DIR/error.npy.
 """
 from __future__ import annotations
 
@@ -36,6 +42,7 @@ HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (spec)
 # profiles/r2_randprobe_sizes.jsonl (~37 G/s; the line, not the byte, is the unit of a random gather)
 RAND_REQ_PEAK = 37.0e9
 STREAM_KERNEL = "k_stream4<8,256,2>"
+MAX_DISTINCT = 512  # distinct query batches held in HBM by the check bench (--steps may be far larger)
 
 
 def parse(argv=None):
@@ -168,7 +175,8 @@ def parse(argv=None):
                          "records between a batch's launches cost ~9 %% of the 20-step line when every batch carries "
                          "them (profiles/r6i_stats_every_ab.jsonl)")
     ap.add_argument("--replay", type=int, default=0,
-                    help="cycle over this many distinct batches (0 = a distinct batch for every step; diagnostics)")
+                    help="cycle over this many distinct batches (0 = a distinct batch for every step, up to 512; "
+                         "diagnostics)")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="CPU-baseline threads (0 = os.cpu_count(), also timed at the affinity count, 16 and 1)")
     ap.add_argument("--preset", type=int, default=0,
@@ -194,7 +202,18 @@ def parse(argv=None):
     ap.add_argument("--expand-gw", type=int, default=1,
                     help="kg_snapshot_tune expand_gw (1: large expand roots gather their neighbourhood, then walk the copy)")
     ap.add_argument("--delta", type=int, default=1000, help="--mode refresh: rows per transaction")
+    ap.add_argument("--full", action="store_true",
+                    help="check mode: after the headline's timed steps also run everything else the line can carry -- "
+                         "the tail tier's roofline phase, the latency phase, the host-path leg, parity against the "
+                         "oracle, the CPU baseline and the C5 / C3 / heavy-tail / sharded sub-lines.  Without it a "
+                         "run sets up, warms up, times --steps steps and prints the headline's line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="check mode: after the timed steps write what the last timed step's kg_check_batch_device "
+                         "call returned as DIR/allowed.npy and DIR/error.npy (float32, one value per check of the "
+                         "batch; the same arguments give the same queries on every run)")
     a = ap.parse_args(argv)
+    if a.dump_outputs and a.mode != "check":
+        ap.error("--dump-outputs writes the check mode's answers (--mode check)")
     if a.hw_queues is None:
         a.hw_queues = 16
     if a.batch is None:
@@ -931,6 +950,13 @@ def aggregate(dist, elapsed: float, edges: float, device=None):
     return float(t[0].item()), float(e[0].item())
 
 
+def dump_outputs(path: str, rank: int, arrays: dict) -> None:
+    """--dump-outputs: every array as <path>/<name>.npy in float32 (rank 0; other ranks add _rank<r>)."""
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + (f"_rank{rank}" if rank else "") + ".npy"), np.asarray(x, np.float32))
+
+
 def spawn_ranks(a, argv) -> int:
     """`bench.py --gpus N` (N > 1) started without a launcher: this process becomes a launcher that never
     touches the GPU.  It starts N children -- this script with the same arguments and RANK / LOCAL_RANK /
@@ -1011,6 +1037,10 @@ def main():
         return bench_host(a)
     if a.mode == "refresh":
         return bench_refresh(a)
+    if not a.full:
+        # the headline alone: every phase after the timed steps, and every sub-line, is --full's
+        a.latency_batches = a.host_calls = a.parity = a.cpu_seconds = 0
+        a.expand_steps = a.c3_steps = a.heavy_steps = a.sharded_steps = 0
     import torch
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1049,7 +1079,9 @@ def main():
     streams = inflight_streams(local, P + a.stream_base)[a.stream_base:]  # --stream-base: diagnostics
     warm = max(a.warmup, P)  # every stream's workspace is allocated before the timed region
     n_batches = warm + a.steps
-    n_distinct = min(n_batches, a.replay) if a.replay > 0 else n_batches
+    # --replay 0: distinct batches up to MAX_DISTINCT (28 MB of queries each), then the cycle repeats -- a batch
+    # comes round again after MAX_DISTINCT others, long after its lines left L2 and the Infinity Cache
+    n_distinct = min(n_batches, a.replay if a.replay > 0 else MAX_DISTINCT)
     dq_all = torch.empty((n_distinct, B, 7), dtype=torch.int32, device=dev)
     for k in range(n_distinct):
         _lib.check(L.kg_synth_queries(snap.handle, 1000 + rank + 7919 * k, B, dq_all[k].data_ptr()),
@@ -1137,6 +1169,10 @@ def main():
     elapsed = time.perf_counter() - t0
     res = timed_out.cpu().numpy()
     errs = torch.cat(derrs).cpu().numpy()
+    if a.dump_outputs:
+        # the last timed step's call: its answers, and the error codes its stream's buffer holds since
+        p_last = (a.steps - 1) % P
+        dump_outputs(a.dump_outputs, rank, {"allowed": res[-1], "error": derrs[p_last].cpu().numpy()})
     assert (errs == 0).all() and (res <= 1).all(), "unexpected errors in the synthetic batch"
     stats = [x for x in stats if x is not None]
     elapsed, edges = aggregate(dist, elapsed, float(sum(s.edges_read for s in stats)) * a.steps / len(stats),
@@ -1145,15 +1181,17 @@ def main():
     rf_stream = stream_roofline(stats, pmc_traffic(STREAM_KERNEL, int(a.tuples), B, a.preset, P, tag))
     # the tail tier's level launches are timed one by one (kg_snapshot_tune "level_events") in a stats phase
     # of their own after the timed region: an event pair per launch leaves gaps in the stream
-    level_events(snap, 1)
-    n_t = min(2 * P, warm)  # warm-up batch indices: their results go to the scratch outputs, not timed_out
-    tstats = [_lib.kg_stats() for _ in range(n_t)]
-    go, th, errs_t = run_steps(0, n_t, tstats)
-    go.set()
-    finish(th, errs_t)
-    torch.cuda.synchronize()
-    level_events(snap, 0)
-    rf_tail = tail_roofline(tstats, lambda k: pmc_traffic(k, int(a.tuples), B, a.preset, P, tag))
+    rf_tail = None
+    if a.full:
+        level_events(snap, 1)
+        n_t = min(2 * P, warm)  # warm-up batch indices: their results go to the scratch outputs, not timed_out
+        tstats = [_lib.kg_stats() for _ in range(n_t)]
+        go, th, errs_t = run_steps(0, n_t, tstats)
+        go.set()
+        finish(th, errs_t)
+        torch.cuda.synchronize()
+        level_events(snap, 0)
+        rf_tail = tail_roofline(tstats, lambda k: pmc_traffic(k, int(a.tuples), B, a.preset, P, tag))
     # the headline keeps k_stream4's roofline (its kernel since round 1); the heavy-tail point reports its
     # dominant kernel by device time per batch (k_ms_level); every measured kernel is in "rooflines"
     rf_main = dominant(rf_stream, rf_tail) if a.heavy_tail else rf_stream
@@ -1216,6 +1254,8 @@ def main():
         "scaling": "weak",
         "vs_baseline": None,
         "dtype": "u32",
+        "full": bool(a.full),
+        "distinct_batches": n_distinct,
         "data": "synthetic (device-generated Drive-like tuple graph, seed %d)" % a.seed,
         "config": {"workload": "%s generator @ %.4g tuples (rows), %d checks/step/GPU, max_read_depth %d"
                                % ("C2/C4" if a.preset == 0 else "C3 (OPL view/edit/share)", info["rows"], B,
@@ -1350,7 +1390,7 @@ def heavy_leg(a) -> dict:
     its own timed region, latency phase, parity against the oracle, CPU baseline and the roofline of its
     dominant kernel (k_ms_level, HIP events per launch)."""
     import subprocess
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--heavy-tail", "--steps", str(a.heavy_steps), "--warmup", "4",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--heavy-tail", "--full", "--steps", str(a.heavy_steps), "--warmup", "4",
            "--cpu-seconds", str(a.cpu_seconds / 3), "--parity", str(a.heavy_parity), "--parity-canonical",
            str(min(a.heavy_parity, 10_000)), "--latency-batches", "120", "--host-calls", "0",
            "--hw-queues", str(a.hw_queues), "--seed", str(a.seed), "--global-depth", str(a.global_depth)]

@@ -3,6 +3,7 @@
 # KG_LIB_PATH) or "-" for the in-tree build.
 # usage: TAG=r2ab VARIANTS="libketogpu_head.so|-|- --resolve-unheld 0" ROUNDS=2 bash scripts/gpu_ab.sh
 set -u
+ARGS="--full ${ARGS:-}"  # the summary below reads the latency phase's p99 (bench.py --full)
 TAG=${TAG:-r2ab}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out

@@ -26,5 +26,6 @@ for K in k_stream4 k_resolve k_back; do
   python3 scripts/pmc_summary.py --kernel $K --fetch gpurun_out/pmc_${TAG}_fetch --write gpurun_out/pmc_${TAG}_write --tuples $TUPLES --batch 1000000 --preset $PRESET --inflight $INFLIGHT --out profiles/pmc_${K}_p${PRESET}.json > /dev/null || true
 done
 cp profiles/pmc_k_*_p${PRESET}.json gpurun_out/ 2>/dev/null || true  # the bench below reads them; copied back for committing
-timeout -k 10 300 python bench.py --cpu-seconds ${CPU:-12} $EXTRA > gpurun_out/bench_${TAG}.log 2>&1; rc=$?; echo "bench rc=$rc"; tail -1 gpurun_out/bench_${TAG}.log | cut -c1-300
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"  # the whole line (--full), with the PMC summaries above in profiles/
+timeout -k 10 300 python bench.py --full --cpu-seconds ${CPU:-12} $EXTRA > "$OUT"/bench_${TAG}.log 2>&1; rc=$?; echo "bench rc=$rc"; tail -1 "$OUT"/bench_${TAG}.log | cut -c1-300
 exit $rc

@@ -4,7 +4,10 @@
 #        bench), BENCH_EXTRA (args of the default bench), BENCH2 (args of a second bench run),
 #        PYTEST_X ("" runs past failures; default -x), PYTEST_TIMEOUT (seconds, 900), KEXPR (pytest -k
 #        expression, may hold spaces)
+#   the default bench is the whole line (bench.py --full: sub-lines, parity, CPU baseline); BENCH2 gets the
+#   arguments it is given
 set -u
+BENCH_EXTRA="--full ${BENCH_EXTRA:-}"
 TAG=${TAG:-r2}
 TESTS=${TESTS:-tests -m gpu}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"

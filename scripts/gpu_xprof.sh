@@ -2,6 +2,7 @@
 # sub-line's exchange protocol at one batch in flight (RCCL kernels included) and its per-exchange
 # timeline.  usage: gpurun -- 'TAG=r5x bash scripts/gpu_xprof.sh'   env: EXTRA (bench args), BENCH (0: skip)
 set -u
+EXTRA="--full ${EXTRA:-}"  # both runs need the sub-lines
 TAG=${TAG:-r5x}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out

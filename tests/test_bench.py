@@ -27,6 +27,23 @@ def test_defaults_and_tune_set():
     assert bench.parse(["--heavy-tail"]).tuples >= 1e8
 
 
+def test_full_and_dump_outputs(tmp_path):
+    """A plain run is the headline alone (--full off, nothing dumped); --dump-outputs writes float32 .npy."""
+    import numpy as np
+    import pytest
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    d = str(tmp_path / "dump")
+    b = bench.parse(["--full", "--dump-outputs", d, "--steps", "7"])
+    assert b.full is True and b.dump_outputs == d and b.steps == 7
+    with pytest.raises(SystemExit):
+        bench.parse(["--mode", "expand", "--dump-outputs", d])
+    bench.dump_outputs(d, 0, {"allowed": np.array([0, 1, 1], np.uint8), "error": np.zeros(3, np.int32)})
+    got = np.load(tmp_path / "dump" / "allowed.npy")
+    assert got.dtype == np.float32 and got.tolist() == [0.0, 1.0, 1.0]
+    assert np.load(tmp_path / "dump" / "error.npy").dtype == np.float32
+
+
 def test_effective_cpus():
     c = bench.effective_cpus()
     assert 1 <= c["effective"] <= c["affinity"] <= c["nproc"]
