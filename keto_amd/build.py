@@ -40,7 +40,7 @@ def build(force: bool = False, verbose: bool = False, out: str = LIB, defines=()
     for src in sources():
         obj = os.path.join(obj_dir, os.path.basename(src) + ".o")
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-c", "-x", "hip", src, "-o", obj,
-               "-I", os.path.join(ROOT, "include"), "-Wall", "-Wno-unused-function", "-Wno-unused-result"]
+               "-I", os.path.join(ROOT, "include"), "-Wall", "-Wno-unused-function"]
         cmd += ["-D" + d for d in defines]
         jobs.append((cmd, src))
         objs.append(obj)

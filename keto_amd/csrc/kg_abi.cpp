@@ -593,7 +593,7 @@ int64_t kg_snapshot_export(const kg_snapshot* sp, kg_tuple* rows, uint64_t cap) 
   if (!sp) return set_error(-2, "NULL snapshot");
   Snapshot* s = const_cast<Snapshot*>(reinterpret_cast<const Snapshot*>(sp));
   std::lock_guard<std::mutex> lk(s->mu);
-  hipSetDevice(s->device);
+  HIPC(hipSetDevice(s->device));
   return s->export_rows(rows, cap);
   KG_GUARD_END
 }
@@ -655,12 +655,11 @@ int kg_check_batch_packed_device(kg_snapshot* sp, const kg_query_packed* d_q, si
     // usual sharded batch (completed before the buffer is freed)
     HIPC(hipSetDevice(s->device));
     hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-    kg_query* dq = nullptr;
-    if (n) HIPC(hipMalloc(&dq, n * sizeof(kg_query)));
+    kg::DevBuf<kg_query> dq;
+    if (n) HIPC(dq.reserve(n));
     int rc = n ? kg::unpack_queries(d_q, n, dq, st) : 0;
     if (!rc) rc = kg_check_batch_device(sp, dq, n, global_max_depth, d_out, d_err, stats, stream);
     if (hipStreamSynchronize(st) != hipSuccess && !rc) rc = set_error(-1, "packed sharded batch");
-    hipFree(dq);
     return rc;
   }
   kg::Workspace* w = s->workspace((hipStream_t)stream);
@@ -677,15 +676,14 @@ int kg_pack_queries_device(kg_snapshot* sp, const kg_query* d_q, size_t n, kg_qu
   Snapshot* s = reinterpret_cast<Snapshot*>(sp);
   HIPC(hipSetDevice(s->device));
   hipStream_t st = stream ? (hipStream_t)stream : s->stream;
-  uint32_t* d_bad = nullptr;
-  HIPC(hipMalloc(&d_bad, 4));
+  kg::DevBuf<uint32_t> d_bad;
+  HIPC(d_bad.reserve(1));
   uint32_t bad = 0;
   int rc = hipMemsetAsync(d_bad, 0, 4, st) != hipSuccess ? set_error(-1, "pack: memset") : 0;
   if (!rc) rc = kg::pack_queries(d_q, n, d_pk, d_bad, st);
   if (!rc && (hipMemcpyAsync(&bad, d_bad, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
               hipStreamSynchronize(st) != hipSuccess))
     rc = set_error(-1, "pack: readback");
-  hipFree(d_bad);
   if (!rc && bad) rc = set_error(-2, "an id does not fit kg_query_packed (use kg_check_batch_device)");
   return rc;
   KG_GUARD_END
@@ -739,8 +737,8 @@ static int check_host(Snapshot* s, const kg_query* q, const kg_query_packed* pq,
     if ((rc = pq ? L->reserve_packed(m) : L->reserve(m))) break;
     HIPC(hipSetDevice(L->device));
     const size_t rec = pq ? sizeof(kg_query_packed) : sizeof(kg_query);
-    char* hs = reinterpret_cast<char*>(L->h_q);
-    char* ds = pq ? reinterpret_cast<char*>(L->d_pk) : reinterpret_cast<char*>(L->d_q);
+    char* hs = reinterpret_cast<char*>(L->h_q.get());
+    char* ds = pq ? reinterpret_cast<char*>(L->d_pk.get()) : reinterpret_cast<char*>(L->d_q.get());
     const char* src = pq ? reinterpret_cast<const char*>(pq + b[i]) : reinterpret_cast<const char*>(q + b[i]);
     for (size_t o = 0; o < m; o += SLICE) {
       const size_t k = std::min(SLICE, m - o);
@@ -765,11 +763,11 @@ static int check_host(Snapshot* s, const kg_query* q, const kg_query_packed* pq,
     kg::Lane* L = lane(i);
     const size_t m = b[i + 1] - b[i];
     if (!rc) {
-      hipSetDevice(L->device);
       bool reran = false;
       // asleep on a blocking-sync event, not spinning (round 2: one spinning core per in-flight batch
       // competed with the server's threads; the "host_sync" knob was removed in round 6)
-      int r2 = kg::check_batch_end(L->rep, L->w, &bp[i], &reran, true);
+      int r2 = hipSetDevice(L->device) != hipSuccess ? set_error(-1, "hipSetDevice(%d) failed", L->device)
+                                                     : kg::check_batch_end(L->rep, L->w, &bp[i], &reran, true);
       if (!r2 && reran &&  // the grid tier rewrote results after the first copy: copy them again
           (hipMemcpyAsync(L->h_out, L->d_out, m, hipMemcpyDeviceToHost, L->stream) != hipSuccess ||
            (!sp && hipMemcpyAsync(L->h_err, L->d_err, m * 4, hipMemcpyDeviceToHost, L->stream) != hipSuccess)))
@@ -799,7 +797,7 @@ static int check_host(Snapshot* s, const kg_query* q, const kg_query_packed* pq,
       }
       rc = r2;
     } else {
-      hipSetDevice(L->device);
+      (void)hipSetDevice(L->device);  // the batch already failed: only drain the lane
       (void)hipStreamSynchronize(L->stream);
     }
     L->w->mu.unlock();

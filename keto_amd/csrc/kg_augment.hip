@@ -33,7 +33,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <functional>
 #include <vector>
 
 #include "kg_bfs.h"
@@ -384,26 +383,13 @@ int Snapshot::augment_rewrites() {
     c_off[i + 1] = c_off[i] + (uint32_t)contrib[i].size();
     c_list.insert(c_list.end(), contrib[i].begin(), contrib[i].end());
   }
-  std::vector<void*> tmp;  // freed at the end
-  auto talloc = [&](void** p, size_t bytes) -> int {
-    HIPC(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    tmp.push_back(*p);
-    return 0;
-  };
-  auto cleanup = [&]() {
-    for (void* p : tmp) hipFree(p);
-    tmp.clear();
-  };
-  struct Guard {
-    std::function<void()> f;
-    ~Guard() { f(); }
-  } guard{cleanup};
+  DevTemps tmp;
   AugPlan* d_plans;
   uint32_t *d_coff, *d_clist, *d_cnt;
   uint8_t* d_virt;
-  if (talloc((void**)&d_plans, plans.size() * sizeof(AugPlan)) || talloc((void**)&d_coff, c_off.size() * 4) ||
-      talloc((void**)&d_clist, c_list.size() * 4 + 4) || talloc((void**)&d_virt, virt.size()) ||
-      talloc((void**)&d_cnt, 16))
+  if (tmp.alloc((void**)&d_plans, plans.size() * sizeof(AugPlan)) || tmp.alloc((void**)&d_coff, c_off.size() * 4) ||
+      tmp.alloc((void**)&d_clist, c_list.size() * 4 + 4) || tmp.alloc((void**)&d_virt, virt.size()) ||
+      tmp.alloc((void**)&d_cnt, 16))
     return -1;
   HIPC(hipMemcpy(d_plans, plans.data(), plans.size() * sizeof(AugPlan), hipMemcpyHostToDevice));
   HIPC(hipMemcpy(d_coff, c_off.data(), c_off.size() * 4, hipMemcpyHostToDevice));
@@ -412,8 +398,8 @@ int Snapshot::augment_rewrites() {
   const AugTables A{d_plans, (uint32_t)plans.size(), d_coff, d_clist, d_virt};
   // the base snapshot needs a node map for the anchor lookups: a keys-only one over the base nodes
   const uint64_t slots0 = std::max<uint64_t>(16, (uint64_t)n0 * 8 / 5);  // load 0.625
-  NSlot* nm0;
-  if (talloc((void**)&nm0, slots0 * sizeof(NSlot))) return -1;
+  DevBuf<NSlot> nm0;
+  HIPC(nm0.reserve(slots0));
   HIPC(hipMemsetAsync(nm0, 0xFF, slots0 * sizeof(NSlot), stream));
   hipLaunchKernelGGL(k_aug_nmap, dim3((n0 + 255) / 256), dim3(256), 0, stream, nm0, slots0, ds.nd_ns, ds.nd_obj,
                      ds.nd_rel, n0);
@@ -423,14 +409,14 @@ int Snapshot::augment_rewrites() {
   // 1. candidates: count per anchor node, scan, place
   uint32_t* ccount;
   uint64_t* cpos;
-  if (talloc((void**)&ccount, ((size_t)n0 + 1) * 4) || talloc((void**)&cpos, ((size_t)n0 + 1) * 8)) return -1;
+  if (tmp.alloc((void**)&ccount, ((size_t)n0 + 1) * 4) || tmp.alloc((void**)&cpos, ((size_t)n0 + 1) * 8)) return -1;
   hipLaunchKernelGGL((k_aug_cands<false>), dim3((n0 + 255) / 256), dim3(256), 0, stream, b, A, n0, ccount, nullptr,
                      nullptr, nullptr, nullptr);
   HIPC(hipMemsetAsync(ccount + n0, 0, 4, stream));
   size_t tb0 = 0;
   HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb0, ccount, cpos, (size_t)n0 + 1, stream));
   void* scr0;
-  if (talloc(&scr0, tb0 + 16)) return -1;
+  if (tmp.alloc(&scr0, tb0 + 16)) return -1;
   HIPC(hipcub::DeviceScan::ExclusiveSum(scr0, tb0, ccount, cpos, (size_t)n0 + 1, stream));
   uint64_t nc64 = 0;
   HIPC(hipMemcpyAsync(&nc64, cpos + n0, 8, hipMemcpyDeviceToHost, stream));
@@ -439,21 +425,20 @@ int Snapshot::augment_rewrites() {
   if (nc64 >= 0x7FFFFFFFull) return set_error(KG_ERR_RESOURCE_CODE, "too many union nodes");
   const uint32_t nc = (uint32_t)nc64;
   uint32_t *c_plan, *c_obj, *c_base, *c_id;
-  if (talloc((void**)&c_plan, (size_t)nc * 4) || talloc((void**)&c_obj, (size_t)nc * 4) ||
-      talloc((void**)&c_base, (size_t)nc * 4) || talloc((void**)&c_id, (size_t)nc * 4))
+  if (tmp.alloc((void**)&c_plan, (size_t)nc * 4) || tmp.alloc((void**)&c_obj, (size_t)nc * 4) ||
+      tmp.alloc((void**)&c_base, (size_t)nc * 4) || tmp.alloc((void**)&c_id, (size_t)nc * 4))
     return -1;
   hipLaunchKernelGGL((k_aug_cands<true>), dim3((n0 + 255) / 256), dim3(256), 0, stream, b, A, n0, nullptr,
                      (const uint64_t*)cpos, c_plan, c_obj, c_base);
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(stream));
-  tmp.erase(std::find(tmp.begin(), tmp.end(), (void*)nm0));  // the base node map is done with
-  HIPC(hipFree(nm0));
+  nm0.reset();  // the base node map is done with
   // 2. ids (new nodes after n0) and the node triples of the extended graph
   if ((uint64_t)n0 + nc >= 0x7FFFFFFFull) return set_error(KG_ERR_RESOURCE_CODE, "too many nodes after materialisation");
   const uint32_t nmax = n0 + nc;  // upper bound (replaced candidates take no new id)
   uint32_t *nd_ns, *nd_obj, *nd_rel, *cand_of;
-  if (talloc((void**)&nd_ns, (size_t)nmax * 4) || talloc((void**)&nd_obj, (size_t)nmax * 4) ||
-      talloc((void**)&nd_rel, (size_t)nmax * 4) || talloc((void**)&cand_of, (size_t)nmax * 4))
+  if (tmp.alloc((void**)&nd_ns, (size_t)nmax * 4) || tmp.alloc((void**)&nd_obj, (size_t)nmax * 4) ||
+      tmp.alloc((void**)&nd_rel, (size_t)nmax * 4) || tmp.alloc((void**)&cand_of, (size_t)nmax * 4))
     return -1;
   HIPC(hipMemcpyAsync(nd_ns, ds.nd_ns, (size_t)n0 * 4, hipMemcpyDeviceToDevice, stream));
   HIPC(hipMemcpyAsync(nd_obj, ds.nd_obj, (size_t)n0 * 4, hipMemcpyDeviceToDevice, stream));
@@ -461,13 +446,13 @@ int Snapshot::augment_rewrites() {
   HIPC(hipMemsetAsync(cand_of, 0xFF, (size_t)nmax * 4, stream));
   uint32_t* is_new;
   uint64_t* new_pos;
-  if (talloc((void**)&is_new, ((size_t)nc + 1) * 4) || talloc((void**)&new_pos, ((size_t)nc + 1) * 8)) return -1;
+  if (tmp.alloc((void**)&is_new, ((size_t)nc + 1) * 4) || tmp.alloc((void**)&new_pos, ((size_t)nc + 1) * 8)) return -1;
   hipLaunchKernelGGL(k_aug_isnew, dim3((nc + 255) / 256), dim3(256), 0, stream, nc, (const uint32_t*)c_base, is_new);
   HIPC(hipMemsetAsync(is_new + nc, 0, 4, stream));
   size_t tb1 = 0;
   HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb1, is_new, new_pos, (size_t)nc + 1, stream));
   void* scr1;
-  if (talloc(&scr1, tb1 + 16)) return -1;
+  if (tmp.alloc(&scr1, tb1 + 16)) return -1;
   HIPC(hipcub::DeviceScan::ExclusiveSum(scr1, tb1, is_new, new_pos, (size_t)nc + 1, stream));
   hipLaunchKernelGGL(k_aug_ids, dim3((nc + 255) / 256), dim3(256), 0, stream, b, A, nc, n0, c_plan, c_obj, c_base,
                      (const uint64_t*)new_pos, c_id, cand_of, nd_ns, nd_obj, nd_rel);
@@ -480,7 +465,7 @@ int Snapshot::augment_rewrites() {
   // node map over every node of the extended graph (keys + ids) for the successor lookups
   const uint64_t slots1 = std::max<uint64_t>(16, (uint64_t)n1 * 8 / 5);
   NSlot* nm1;
-  if (talloc((void**)&nm1, slots1 * sizeof(NSlot))) return -1;
+  if (tmp.alloc((void**)&nm1, slots1 * sizeof(NSlot))) return -1;
   HIPC(hipMemsetAsync(nm1, 0xFF, slots1 * sizeof(NSlot), stream));
   hipLaunchKernelGGL(k_aug_nmap, dim3((n1 + 255) / 256), dim3(256), 0, stream, nm1, slots1, nd_ns, nd_obj, nd_rel,
                      n1);
@@ -493,7 +478,7 @@ int Snapshot::augment_rewrites() {
   x.nd_rel = nd_rel;
   // 3. purity fixpoint
   uint8_t* imp;
-  if (talloc((void**)&imp, (size_t)n1 + 16)) return -1;
+  if (tmp.alloc((void**)&imp, (size_t)n1 + 16)) return -1;
   const uint32_t g1 = (n1 + 255) / 256;
   hipLaunchKernelGGL(k_aug_seed, dim3(g1), dim3(256), 0, stream, x, b, A, n1, cand_of, c_plan, c_obj, imp,
                      shard_rank, shard_n);
@@ -514,7 +499,7 @@ int Snapshot::augment_rewrites() {
   }
   // 4. augmented set-adjacency and check rows
   uint64_t *adeg, *cdeg;
-  if (talloc((void**)&adeg, ((size_t)n1 + 1) * 8) || talloc((void**)&cdeg, ((size_t)n1 + 1) * 8)) return -1;
+  if (tmp.alloc((void**)&adeg, ((size_t)n1 + 1) * 8) || tmp.alloc((void**)&cdeg, ((size_t)n1 + 1) * 8)) return -1;
   hipLaunchKernelGGL(k_aug_len, dim3(g1), dim3(256), 0, stream, x, b, A, n1, cand_of, c_plan, c_obj, imp, adeg, cdeg);
   HIPC(hipGetLastError());
   HIPC(hipMemsetAsync(adeg + n1, 0, 8, stream));
@@ -527,7 +512,7 @@ int Snapshot::augment_rewrites() {
   size_t tb = 0;
   HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, adeg, aoff, (size_t)n1 + 1, stream));
   void* scratch;
-  if (talloc(&scratch, tb + 16)) return -1;
+  if (tmp.alloc(&scratch, tb + 16)) return -1;
   HIPC(hipcub::DeviceScan::ExclusiveSum(scratch, tb, adeg, aoff, (size_t)n1 + 1, stream));
   HIPC(hipcub::DeviceScan::ExclusiveSum(scratch, tb, cdeg, coff, (size_t)n1 + 1, stream));
   uint64_t tot[2];

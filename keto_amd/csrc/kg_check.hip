@@ -982,13 +982,7 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
   const uint4* pq = nullptr;
   if (d_pk && n) {
     if (s->n_fplans || s->ds.relflags || s->ds.nflags) {
-      if (n > w->unpacked_n) {
-        if (w->unpacked) hipFree(w->unpacked);
-        w->unpacked = nullptr;
-        w->unpacked_n = 0;
-        HIPC(hipMalloc(&w->unpacked, n * sizeof(kg_query)));
-        w->unpacked_n = n;
-      }
+      HIPC(w->unpacked.reserve(n));
       if (int rc = unpack_queries(d_pk, n, w->unpacked, stream)) return rc;
       d_q = w->unpacked;
     } else {
@@ -1034,18 +1028,14 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
   };
   size_t off[8];
   const size_t total = layout(n, off);
-  if (total > w->scratch_bytes) {  // sized for >= 64 Ki queries, grown geometrically (hipFree stalls the device)
+  if (total > w->scratch.cap()) {  // sized for >= 64 Ki queries, grown geometrically (hipFree stalls the device)
     const size_t m = std::max<size_t>(65536, std::max<size_t>(2 * w->scratch_n, n));
     size_t tmp[8];
     const size_t want = layout(m, tmp);
-    if (w->scratch) hipFree(w->scratch);
-    w->scratch = nullptr;
-    w->scratch_bytes = 0;
-    HIPC(hipMalloc(&w->scratch, want));
-    w->scratch_bytes = want;
+    HIPC(w->scratch.reserve(want));
     w->scratch_n = m;
   }
-  char* base = (char*)w->scratch;
+  char* base = (char*)w->scratch.get();
   RQuery* rq = (RQuery*)(base + off[0]);
   LQuery* lq = (LQuery*)(base + off[1]);
   uint32_t* gen = (uint32_t*)(base + off[2]);

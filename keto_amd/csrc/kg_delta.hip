@@ -290,23 +290,12 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   std::vector<uint64_t> h_ik(iv.size());
   for (size_t i = 0; i < iv.size(); i++) h_in[i] = iv[i].node, h_is[i] = iv[i].subj, h_ik[i] = iv[i].key;
   for (size_t i = 0; i < dv.size(); i++) h_dn[i] = dv[i].first, h_dsub[i] = dv[i].second;
-  std::vector<void*> tmp;
-  struct Free {
-    std::vector<void*>& t;
-    ~Free() {
-      for (void* p : t) hipFree(p);
-    }
-  } free_tmp{tmp};
-  auto talloc = [&](void** p, size_t bytes) -> int {
-    HIPC(hipMalloc(p, std::max<size_t>(bytes, 16)));
-    tmp.push_back(*p);
-    return 0;
-  };
+  DevTemps tmp;
   uint32_t *d_in, *d_is, *d_dn, *d_ds;
   uint64_t* d_ik;
-  if (talloc((void**)&d_in, h_in.size() * 4) || talloc((void**)&d_is, h_is.size() * 4) ||
-      talloc((void**)&d_ik, h_ik.size() * 8) || talloc((void**)&d_dn, h_dn.size() * 4) ||
-      talloc((void**)&d_ds, h_dsub.size() * 4))
+  if (tmp.alloc((void**)&d_in, h_in.size() * 4) || tmp.alloc((void**)&d_is, h_is.size() * 4) ||
+      tmp.alloc((void**)&d_ik, h_ik.size() * 8) || tmp.alloc((void**)&d_dn, h_dn.size() * 4) ||
+      tmp.alloc((void**)&d_ds, h_dsub.size() * 4))
     return -1;
   if (!h_in.empty()) {
     HIPC(hipMemcpyAsync(d_in, h_in.data(), h_in.size() * 4, hipMemcpyHostToDevice, stream));
@@ -335,7 +324,7 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   // copy of untouched rows, scatter of kept + inserted entries of touched rows
   uint64_t *newlen, *d_ro;
   uint8_t* touched;
-  if (talloc((void**)&newlen, ((size_t)n1 + 1) * 8) || talloc((void**)&touched, (size_t)n1 + 16) ||
+  if (tmp.alloc((void**)&newlen, ((size_t)n1 + 1) * 8) || tmp.alloc((void**)&touched, (size_t)n1 + 16) ||
       alloc((void**)&d_ro, ((size_t)n1 + 1) * 8))
     return -1;
   const uint32_t g1 = (n1 + 255) / 256;
@@ -353,8 +342,8 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   // their old row lengths scanned into flat offsets (toff), and node -> touched index (tslot)
   uint32_t *d_tl, *d_tslot;
   uint64_t *d_tlen, *d_toff;
-  if (talloc((void**)&d_tl, (size_t)n_t * 4) || talloc((void**)&d_tlen, ((size_t)n_t + 1) * 8) ||
-      talloc((void**)&d_toff, ((size_t)n_t + 1) * 8) || talloc((void**)&d_tslot, (size_t)n1 * 4))
+  if (tmp.alloc((void**)&d_tl, (size_t)n_t * 4) || tmp.alloc((void**)&d_tlen, ((size_t)n_t + 1) * 8) ||
+      tmp.alloc((void**)&d_toff, ((size_t)n_t + 1) * 8) || tmp.alloc((void**)&d_tslot, (size_t)n1 * 4))
     return -1;
   uint64_t F = 0;
   if (n_t) {
@@ -368,14 +357,14 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
     size_t t0b = 0;
     HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, t0b, d_tlen, d_toff, (size_t)n_t + 1, stream));
     void* t0s;
-    if (talloc(&t0s, t0b + 16)) return -1;
+    if (tmp.alloc(&t0s, t0b + 16)) return -1;
     HIPC(hipcub::DeviceScan::ExclusiveSum(t0s, t0b, d_tlen, d_toff, (size_t)n_t + 1, stream));
     HIPC(hipMemcpyAsync(&F, d_toff + n_t, 8, hipMemcpyDeviceToHost, stream));
     HIPC(hipStreamSynchronize(stream));
   }
   uint32_t* d_keep;
   uint64_t* d_kr;
-  if (talloc((void**)&d_keep, F * 4 + 4) || talloc((void**)&d_kr, (F + 1) * 8)) return -1;
+  if (tmp.alloc((void**)&d_keep, F * 4 + 4) || tmp.alloc((void**)&d_kr, (F + 1) * 8)) return -1;
   void* scratch = nullptr;
   size_t tb = 0, tb2 = 0;
   HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, newlen, d_ro, (size_t)n1 + 1, stream));
@@ -394,7 +383,7 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, (const uint32_t*)nullptr, (uint64_t*)nullptr, (size_t)n_rows_max + 1,
                                         stream));
   tb = std::max(tb, tb3);
-  if (talloc(&scratch, tb + 16)) return -1;
+  if (tmp.alloc(&scratch, tb + 16)) return -1;
   HIPC(hipcub::DeviceScan::ExclusiveSum(scratch, tb, d_keep, d_kr, (size_t)F + 1, stream));
   if (n_t) {
     hipLaunchKernelGGL(k_delta_tlen, dim3((n_t + 255) / 256), dim3(256), 0, stream, (const uint32_t*)d_tl, n_t,
@@ -427,7 +416,7 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   // 5. set-adjacency: a flag per row entry, scanned into positions
   uint32_t* flag;
   uint64_t* pos;
-  if (talloc((void**)&flag, total * 4 + 8) || talloc((void**)&pos, (total + 1) * 8)) return -1;
+  if (tmp.alloc((void**)&flag, total * 4 + 8) || tmp.alloc((void**)&pos, (total + 1) * 8)) return -1;
   if (total)
     hipLaunchKernelGGL(k_delta_isadj, dim3(2048), dim3(256), 0, stream, (const uint32_t*)d_rs, total,
                        (const uint32_t*)d_rel, wildcard_rel, flag);

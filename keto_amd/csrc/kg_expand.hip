@@ -947,7 +947,7 @@ __global__ __launch_bounds__(256) void k_expand_gw(DevSnap s, const kg_set* __re
                                                    uint32_t n_roots, uint32_t n_big, GwSlots g_small, GwSlots g_big,
                                                    uint64_t wait_ticks) {
   __shared__ uint32_t vis[GW_LDS_LOC / 32];
-  __shared__ uint32_t s_k, s_nloc, s_nent, s_bad, s_epoch, s_ri, s_src, s_p2dry;
+  __shared__ uint32_t s_nloc, s_nent, s_bad, s_epoch, s_ri, s_src, s_p2dry;
   __shared__ ExpFrame s_fr[XF];
   // The walk's records are staged in LDS and leave one full arena chunk at a time: on CDNA a wave's
   // vmcnt counts stores as well as loads, so a record store per step made every next load of the copy
@@ -1385,31 +1385,25 @@ __global__ void k_root_counts(const RootOut* outs, uint32_t n, unsigned long lon
 // serialise concurrent callers.
 struct ExpandBufs {
   int device = -1;
-  kg_set* d_roots = nullptr;
-  RootOut* outs = nullptr;
-  uint32_t* p2 = nullptr;  // pass-2 | pass-3 queues
-  size_t n_cap = 0;        // roots the three above hold
-  ExpCtl* ctl = nullptr;
-  ExpFrame* stacks = nullptr;
-  size_t stacks_bytes = 0;
-  uint32_t* bm = nullptr;  // [pass-2 tables | pass-3 bitmap] | pass-2 lists | pass-3 list
-  size_t bm_bytes = 0;
+  DevBuf<kg_set> d_roots;
+  DevBuf<RootOut> outs;
+  DevBuf<uint32_t> p2;  // pass-2 | pass-3 queues
+  size_t n_cap = 0;     // roots the three above hold
+  DevBuf<ExpCtl> ctl;
+  DevBuf<ExpFrame> stacks;
+  DevBuf<uint32_t> bm;  // [pass-2 tables | pass-3 bitmap] | pass-2 lists | pass-3 list
   // the pass-2 tables and the pass-3 bitmap need clearing: fresh memory, or a call that ended early (an
   // arena rerun or an error can leave keys behind; a completed call leaves them clear -- every root's
   // walk removes its keys, an overflowing one zeroes its table)
   bool bm_dirty = true;
-  kg_tree_node* arena = nullptr;
-  uint32_t* next = nullptr;
+  DevBuf<kg_tree_node> arena;
+  DevBuf<uint32_t> next;
   uint32_t chunks = 0;
-  kg_tree_node* dst = nullptr;
-  size_t dst_cap = 0;
-  uint64_t* d_off = nullptr;
-  size_t off_cap = 0;
-  unsigned long long* cnt = nullptr;  // device-resident trees: per-root counts (+ total, + overflow tally)
-  size_t cnt_cap = 0;
-  void* scan_tmp = nullptr;  // hipcub scan temporary
-  size_t scan_cap = 0;
-  void* gw[2] = {nullptr, nullptr};  // gather-walk slots: small, large (allocated once, epochs zeroed)
+  DevBuf<kg_tree_node> dst;
+  DevBuf<uint64_t> d_off;
+  DevBuf<unsigned long long> cnt;  // device-resident trees: per-root counts (+ total, + overflow tally)
+  DevBuf<void> scan_tmp;           // hipcub scan temporary
+  DevBuf<char> gw[2];              // gather-walk slots: small, large (allocated once, epochs zeroed)
   GwSlots gws[2] = {};
   uint32_t gw_slots[2] = {0, 0};
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -1423,13 +1417,10 @@ struct ExpandBufs {
     return hipEventSynchronize(sync_ev);
   }
   ~ExpandBufs() {
-    if (device >= 0) hipSetDevice(device);
-    for (void* p : {(void*)d_roots, (void*)outs, (void*)p2, (void*)ctl, (void*)stacks, (void*)bm, (void*)arena,
-                    (void*)next, (void*)dst, (void*)d_off, (void*)cnt, scan_tmp, gw[0], gw[1]})
-      if (p) hipFree(p);
+    if (device >= 0) (void)hipSetDevice(device);
     for (auto& e : ev)
-      if (e) hipEventDestroy(e);
-    if (sync_ev) hipEventDestroy(sync_ev);
+      if (e) (void)hipEventDestroy(e);
+    if (sync_ev) (void)hipEventDestroy(sync_ev);
   }
 };
 
@@ -1438,127 +1429,46 @@ void expand_bufs_free(void* p) { delete static_cast<ExpandBufs*>(p); }
 // Tree outputs go to pinned host memory from a process-wide pool: a device->host copy of a C5
 // batch's ~130 MB of records into fresh pageable memory took ~50 ms (page faults + staging), more
 // than the batch's kernels once batches overlap.  Buffers are size-classed (powers of two from
-// 1 MiB) and returned by kg_tree_free; at most POOL_KEEP bytes stay cached.
-namespace {
-constexpr size_t POOL_KEEP = 4ull << 30;
-std::mutex pool_mu;
-std::vector<std::pair<size_t, void*>> pool_free;
-size_t pool_cached = 0;
-size_t pool_class(size_t bytes) {
-  size_t c = 1 << 20;
-  while (c < bytes) c <<= 1;
-  return c;
-}
-}  // namespace
+// 1 MiB) and returned by kg_tree_free; at most 4 GiB stay cached.
+static BlockPool<PinnedMem> pinned_pool(4ull << 30);
 
 void* tree_pool_get(size_t bytes) {
-  const size_t c = pool_class(bytes);
-  {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    for (size_t i = 0; i < pool_free.size(); i++)
-      if (pool_free[i].first == c) {
-        void* p = pool_free[i].second;
-        pool_free[i] = pool_free.back();
-        pool_free.pop_back();
-        pool_cached -= c;
-        return p;
-      }
-  }
-  void* p = nullptr;
-  if (hipHostMalloc(&p, c, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
+  void* p = pinned_pool.get(0, bytes);
+  if (!p) (void)hipGetLastError();
   return p;
 }
 
-void tree_pool_put(void* p, size_t bytes) {
-  if (!p) return;
-  const size_t c = pool_class(bytes);
-  {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    if (pool_cached + c <= POOL_KEEP) {
-      pool_free.emplace_back(c, p);
-      pool_cached += c;
-      return;
-    }
-  }
-  (void)hipHostFree(p);
-}
+void tree_pool_put(void* p, size_t bytes) { pinned_pool.put(0, p, bytes); }
 
 // Device-resident tree outputs (kg_expand_batch_device) come from a per-device pool of the same size
 // classes, returned by kg_tree_free: hipMalloc / hipFree per call stall the device.  At most
-// DEV_POOL_KEEP bytes per device stay cached (C5: ~90 MB of records per call, 16 calls in flight).
-namespace {
-constexpr size_t DEV_POOL_KEEP = 16ull << 30;
-struct DevFree {
-  int device;
-  size_t cls;
-  void* p;
-};
-std::vector<DevFree> dev_free;
-size_t dev_cached[64] = {};
-}  // namespace
+// 16 GiB per device stay cached (C5: ~90 MB of records per call, 16 calls in flight).
+static BlockPool<DeviceMem> dev_pool(16ull << 30);
 
 void* tree_dev_get(int device, size_t bytes) {
-  const size_t c = pool_class(bytes);
-  {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    for (size_t i = 0; i < dev_free.size(); i++)
-      if (dev_free[i].device == device && dev_free[i].cls == c) {
-        void* p = dev_free[i].p;
-        dev_free[i] = dev_free.back();
-        dev_free.pop_back();
-        dev_cached[device & 63] -= c;
-        return p;
-      }
-  }
-  void* p = nullptr;
-  if (hipSetDevice(device) != hipSuccess || hipMalloc(&p, c) != hipSuccess) {
-    (void)hipGetLastError();
-    return nullptr;
-  }
+  void* p = hipSetDevice(device) == hipSuccess ? dev_pool.get(device, bytes) : nullptr;
+  if (!p) (void)hipGetLastError();
   return p;
 }
 
 void tree_dev_put(int device, void* p, size_t bytes) {
-  if (!p) return;
-  const size_t c = pool_class(bytes);
-  {
-    std::lock_guard<std::mutex> lk(pool_mu);
-    if (dev_cached[device & 63] + c <= DEV_POOL_KEEP) {
-      dev_free.push_back(DevFree{device, c, p});
-      dev_cached[device & 63] += c;
-      return;
-    }
-  }
-  (void)hipSetDevice(device);
-  (void)hipFree(p);
-}
-
-// Replaces *p with a buffer of at least `need` bytes (contents not kept).
-template <class T>
-static hipError_t grow(T** p, size_t& have, size_t need) {
-  if (need <= have && *p) return hipSuccess;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  have = 0;
-  const hipError_t e = hipMalloc((void**)p, std::max<size_t>(need, 16));
-  if (e == hipSuccess) have = need;
-  return e;
+  if (!p || dev_pool.keep(device, p, bytes)) return;
+  (void)hipSetDevice(device);  // only a block the pool does not keep needs the device (kg_tree_free: any thread)
+  DeviceMem::free(p);
 }
 
 // Gather-walk slot classes: (slots, entries, map slots, local ids).  Small:
 // the bulk of the pass-1 overflows (~1 k C5 roots of 0.5-10 k records); large: the few giant trees.
 constexpr uint32_t GW_LOC[2] = {16384, GW_LDS_LOC};
 static hipError_t gw_alloc(ExpandBufs& B, int k, uint32_t slots, uint32_t ent_cap, hipStream_t stream) {
-  if (B.gw[k]) return hipSuccess;
+  if (!B.gw[k].empty()) return hipSuccess;
   const uint32_t map_cap = 2 * GW_LOC[k];
   const size_t tf = ent_cap / 64 + 1;
   const size_t per = (size_t)ent_cap * (sizeof(GwEnt) + 8 + 4) + tf * 4 + (size_t)map_cap * 16;
-  char* p = nullptr;
-  hipError_t e = hipMalloc((void**)&p, per * slots + (size_t)slots * 4 + 256);
+  DevBuf<char> buf;
+  hipError_t e = (hipError_t)buf.reserve(per * slots + (size_t)slots * 4 + 256);
   if (e != hipSuccess) return e;
+  char* p = buf;
   GwSlots g{};
   g.ent_cap = ent_cap;
   g.map_cap = map_cap;
@@ -1576,11 +1486,8 @@ static hipError_t gw_alloc(ExpandBufs& B, int k, uint32_t slots, uint32_t ent_ca
   g.ent = (GwEnt*)take((size_t)slots * ent_cap * sizeof(GwEnt));
   g.hsrc = (uint64_t*)take((size_t)slots * ent_cap * 8);
   g.tfirst = (uint32_t*)take((size_t)slots * tf * 4);
-  if ((e = hipMemsetAsync(p, 0, zero, stream)) != hipSuccess) {
-    hipFree(p);
-    return e;
-  }
-  B.gw[k] = p;
+  if ((e = hipMemsetAsync(p, 0, zero, stream)) != hipSuccess) return e;
+  B.gw[k] = std::move(buf);
   B.gws[k] = g;
   B.gw_slots[k] = slots;
   return hipSuccess;
@@ -1631,20 +1538,19 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
   const size_t clear_words = (size_t)slots2 * tsize + words;
   int rc = 0;
   auto fail = [&](const char* what, hipError_t e) { rc = set_error(-1, "%s: %s", what, hipGetErrorString(e)); };
+  auto grow = [](auto& buf, size_t n) { return (hipError_t)buf.reserve(n); };
   hipError_t e = hipSuccess;
   if (n > B.n_cap) {
-    size_t a = 0, b = 0, c = 0;
     const size_t cap = std::max(n, 2 * B.n_cap);
     B.n_cap = 0;
-    if ((e = grow(&B.d_roots, a, cap * sizeof(kg_set))) != hipSuccess || (e = grow(&B.outs, b, cap * sizeof(RootOut))) != hipSuccess ||
-        (e = grow(&B.p2, c, cap * 20)) != hipSuccess)  // p2 | p3 | ga | gb | p0 queues
+    if ((e = grow(B.d_roots, cap)) != hipSuccess || (e = grow(B.outs, cap)) != hipSuccess ||
+        (e = grow(B.p2, cap * 5)) != hipSuccess)  // p2 | p3 | ga | gb | p0 queues
       fail("hipMalloc", e);
     else
       B.n_cap = cap;
   }
-  if (!rc && !B.ctl && (e = hipMalloc(&B.ctl, sizeof(ExpCtl))) != hipSuccess) fail("hipMalloc", e);
-  if (!rc && (e = grow(&B.stacks, B.stacks_bytes,
-                       (size_t)(slots1 + slots2 + 1 + gw_n[0] + gw_n[1] + slots0) * stack_cap * sizeof(ExpFrame))) != hipSuccess)
+  if (!rc && (e = grow(B.ctl, 1)) != hipSuccess) fail("hipMalloc", e);
+  if (!rc && (e = grow(B.stacks, (size_t)(slots1 + slots2 + 1 + gw_n[0] + gw_n[1] + slots0) * stack_cap)) != hipSuccess)
     fail("hipMalloc", e);
   // gather-walk slots (~0.9 GB a lane); without them the pass-1 overflows go to the hash pass directly
   for (int k = 0; k < 2 && gw_on && !rc; k++)
@@ -1654,7 +1560,7 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     }
   {
     const uint32_t* bm0 = B.bm;
-    if (!rc && (e = grow(&B.bm, B.bm_bytes, (clear_words + (size_t)slots2 * cap2 + nn) * 4)) != hipSuccess)
+    if (!rc && (e = grow(B.bm, clear_words + (size_t)slots2 * cap2 + nn)) != hipSuccess)
       fail("hipMalloc", e);
     if (B.bm != bm0) B.bm_dirty = true;
   }
@@ -1668,10 +1574,8 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
   ExpCtl h{};
   for (int attempt = 0; !rc; attempt++) {
     if (n_chunks > B.chunks) {
-      size_t a = 0, b = 0;
       B.chunks = 0;
-      if ((e = grow(&B.arena, a, (size_t)n_chunks * CHUNK * sizeof(kg_tree_node))) != hipSuccess ||
-          (e = grow(&B.next, b, (size_t)n_chunks * 4)) != hipSuccess) {
+      if ((e = grow(B.arena, (size_t)n_chunks * CHUNK)) != hipSuccess || (e = grow(B.next, n_chunks)) != hipSuccess) {
         fail("hipMalloc(arena)", e);
         break;
       }
@@ -1745,16 +1649,16 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     // readback, then the records are compacted into the output (no host pass over the roots)
     uint64_t tail[2] = {0, 0};
     size_t tmp_need = 0;
-    if (!rc && (e = grow(&B.cnt, B.cnt_cap, (n + 2) * 8)) != hipSuccess) fail("hipMalloc", e);
-    if (!rc && (e = hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_need, B.cnt, (unsigned long long*)out->root_off,
+    if (!rc && (e = grow(B.cnt, n + 2)) != hipSuccess) fail("hipMalloc", e);
+    if (!rc && (e = hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_need, B.cnt.get(), (unsigned long long*)out->root_off,
                                                      (int)(n + 1), stream)) != hipSuccess)
       fail("scan", e);
-    if (!rc && (e = grow((char**)&B.scan_tmp, B.scan_cap, tmp_need)) != hipSuccess) fail("hipMalloc", e);
+    if (!rc && (e = grow(B.scan_tmp, std::max<size_t>(tmp_need, 16))) != hipSuccess) fail("hipMalloc", e);
     if (!rc && (e = hipMemsetAsync(B.cnt + n + 1, 0, 8, stream)) != hipSuccess) fail("memset", e);
     if (!rc) {
       hipLaunchKernelGGL(k_root_counts, dim3((uint32_t)((n + 1 + 255) / 256)), dim3(256), 0, stream, B.outs, (uint32_t)n,
                          B.cnt);
-      if ((e = hipcub::DeviceScan::ExclusiveSum(B.scan_tmp, tmp_need, B.cnt, (unsigned long long*)out->root_off,
+      if ((e = hipcub::DeviceScan::ExclusiveSum(B.scan_tmp, tmp_need, B.cnt.get(), (unsigned long long*)out->root_off,
                                                 (int)(n + 1), stream)) != hipSuccess ||
           (e = hipMemcpyAsync(&tail[0], out->root_off + n, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
           (e = hipMemcpyAsync(&tail[1], B.cnt + n + 1, 8, hipMemcpyDeviceToHost, stream)) != hipSuccess ||
@@ -1809,11 +1713,9 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     // grown only when this call's records do not fit, then to twice the old size at least (a request
     // of "twice the capacity" on every call doubled the buffer per call: a long-lived lane ran the
     // device out of memory)
-    const size_t dst_need = total * sizeof(kg_tree_node);
-    if (!rc && dst_need > B.dst_cap &&
-        (e = grow(&B.dst, B.dst_cap, std::max<size_t>(dst_need, 2 * B.dst_cap))) != hipSuccess)
+    if (!rc && total > B.dst.cap() && (e = grow(B.dst, std::max<size_t>(total, 2 * B.dst.cap()))) != hipSuccess)
       fail("hipMalloc", e);
-    if (!rc && (e = grow(&B.d_off, B.off_cap, (n + 1) * 8)) != hipSuccess) fail("hipMalloc", e);
+    if (!rc && (e = grow(B.d_off, n + 1)) != hipSuccess) fail("hipMalloc", e);
     if (!rc && (e = hipMemcpyAsync(B.d_off, out->root_off, (n + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess)
       fail("H2D", e);
     if (!rc) {

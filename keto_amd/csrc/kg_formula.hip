@@ -230,14 +230,13 @@ int Snapshot::build_formulas() {
   // which plans need per-query lookups (own rows, impure leaf nodes)
   std::vector<uint32_t> rs(idx.size(), 0);
   if (ds.n_nodes) {
-    uint32_t* d_rs = nullptr;
-    HIPC(hipMalloc(&d_rs, rs.size() * 4 + 4));
+    DevBuf<uint32_t> d_rs;
+    HIPC(d_rs.reserve(rs.size() + 1));
     HIPC(hipMemsetAsync(d_rs, 0, rs.size() * 4, stream));
     hipLaunchKernelGGL(k_relstats, dim3((ds.n_nodes + 255) / 256), dim3(256), 0, stream, ds, d_rs);
     HIPC(hipGetLastError());
     HIPC(hipMemcpyAsync(rs.data(), d_rs, rs.size() * 4, hipMemcpyDeviceToHost, stream));
     HIPC(hipStreamSynchronize(stream));
-    HIPC(hipFree(d_rs));
   }
   for (uint32_t ns = 0; ns < n_ns; ns++)
     for (uint32_t R = 0; R < n_rel; R++) {
@@ -271,15 +270,9 @@ int formula_split(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, int3
   };
   size_t off[5];
   const size_t need = layout(n, N2, off);
-  if (need > w->split_bytes) {  // grown geometrically like the batch scratch
-    const size_t want = std::max(need, 2 * w->split_bytes);
-    if (w->split) hipFree(w->split);
-    w->split = nullptr;
-    w->split_bytes = 0;
-    HIPC(hipMalloc(&w->split, want));
-    w->split_bytes = want;
-  }
-  char* b = (char*)w->split;
+  if (need > w->split.cap())  // grown geometrically like the batch scratch
+    HIPC(w->split.reserve(std::max(need, 2 * w->split.cap())));
+  char* b = (char*)w->split.get();
   kg_query* q = (kg_query*)(b + off[0]);
   uint2* r = (uint2*)(b + off[3]);
   uint32_t* cnt = (uint32_t*)(b + off[4]);

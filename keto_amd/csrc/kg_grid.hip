@@ -500,14 +500,15 @@ static int grid_layout(GridPool* P, uint64_t cap, hipStream_t stream, GridView* 
   while (hcap < 2 * cap) hcap <<= 1;
   const size_t log_bytes = cap * (4 + 4 + 8 + 8) + 2 * TILE_CAP * 4;
   const size_t need = hcap * 8 + log_bytes + (size_t)G0 * 16 + sizeof(GridCtl) + 4096;
-  if (need > P->bytes) {
+  if (need > P->mem.cap()) {
     P->release();
-    HIPC(hipMalloc(&P->mem, need));
-    HIPC(hipMemsetAsync(P->mem, 0, hcap * 8, stream));  // epoch 0 = empty
-    P->bytes = need;
+    HIPC(P->mem.reserve(need));
+    const hipError_t e = hipMemsetAsync(P->mem, 0, hcap * 8, stream);  // epoch 0 = empty
+    if (e != hipSuccess) P->release();  // not a pool with a table that was never cleared
+    HIPC(e);
   }
   P->cap = cap;
-  char* p = (char*)P->mem;
+  char* p = (char*)P->mem.get();
   v->cap = cap;
   v->hcap = hcap;
   v->H = (uint64_t*)p;

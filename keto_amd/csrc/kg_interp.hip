@@ -616,26 +616,23 @@ int launch_general(Snapshot* s, Workspace* w, const kg_query* d_q, const RQuery*
   const size_t bytes3 = slot_bytes + (words + nn) * 4;
   const size_t tail = (size_t)std::max<uint32_t>(n_queries, 1) * 4;
   size_t need = bytes1 + (size_t)slots2 * per2 + bytes3 + tail;
-  if (need > w->interp_pool_bytes) {
-    if (w->interp_pool) hipFree(w->interp_pool);
-    w->interp_pool = nullptr;
-    w->interp_pool_bytes = 0;
+  if (need > w->interp_pool.cap()) {
+    w->interp_pool.reset();
     // HBM is shared with the snapshot and the other streams' workspaces: fewer pass-2 slots on OOM
     hipError_t e;
-    while ((e = hipMalloc(&w->interp_pool, need)) == hipErrorOutOfMemory && slots2 > 1) {
+    while ((e = (hipError_t)w->interp_pool.reserve(need)) == hipErrorOutOfMemory && slots2 > 1) {
       (void)hipGetLastError();
       slots2 = slots2 / 2;
       need = bytes1 + (size_t)slots2 * per2 + bytes3 + tail;
     }
     HIPC(e);
     HIPC(hipMemsetAsync(w->interp_pool, 0, need, stream));  // memo tags 0 = empty; tables clear
-    w->interp_pool_bytes = need;
   } else if (w->interp_layout != ((uint64_t)slots2 << 40 | (uint64_t)slots1 << 24 | cap2)) {
     HIPC(hipMemsetAsync(w->interp_pool, 0, need, stream));  // regions moved: tables must start clear
   }
   w->interp_layout = (uint64_t)slots2 << 40 | (uint64_t)slots1 << 24 | cap2;
   const size_t bytes2 = (size_t)slots2 * per2;
-  char* p = (char*)w->interp_pool;
+  char* p = (char*)w->interp_pool.get();
   Frame* stacks1 = (Frame*)p;
   MemoEnt* memos1 = (MemoEnt*)(p + (size_t)slots1 * STACK_CAP * sizeof(Frame));
   char* p2 = p + bytes1;

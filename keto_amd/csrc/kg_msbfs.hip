@@ -581,12 +581,11 @@ int ms_layout(GridPool* P, uint32_t n, int K, uint32_t G, uint64_t cap, MsView* 
   const size_t need = 4 * gn + 2 * small + al((size_t)G * 4) + 2 * al((size_t)G * MS_HOPS * K * 8) +
                       3 * al((size_t)G * 64 * K * 4) + al((size_t)G * n * 4) +
                       3 * (al(cap * 8) + 3 * al(cap * 4) + al(MS_TILE_CAP * 4)) + al(sizeof(MsCtl)) + 8192;
-  if (need > P->bytes) {
+  if (need > P->mem.cap()) {
     P->release();
-    HIPC(hipMalloc(&P->mem, need));
-    P->bytes = need;
+    HIPC(P->mem.reserve(need));
   }
-  char* p = (char*)P->mem;
+  char* p = (char*)P->mem.get();
   auto take = [&](size_t bytes) {
     char* q = p;
     p += al(bytes);

@@ -48,56 +48,34 @@ int64_t Snapshot::rows_of(const kg_set* keys, size_t n, uint64_t* offsets, kg_tu
   HIPC(hipSetDevice(device));
   offsets[0] = 0;
   if (!n) return 0;
-  kg_set* d_keys = nullptr;
-  uint32_t* d_node = nullptr;
-  uint64_t* d_len = nullptr;
-  kg_tuple* d_out = nullptr;
-  int64_t rc = -1;
+  DevBuf<kg_set> d_keys;
+  DevBuf<uint32_t> d_node;
+  DevBuf<uint64_t> d_len;
+  DevBuf<kg_tuple> d_out;
   std::vector<uint64_t> len(n);
-  auto done = [&]() {
-    hipFree(d_keys);
-    hipFree(d_node);
-    hipFree(d_len);
-    hipFree(d_out);
-    return rc;
-  };
-  if (hipMalloc(&d_keys, n * sizeof(kg_set)) != hipSuccess || hipMalloc(&d_node, n * 4) != hipSuccess ||
-      hipMalloc(&d_len, (n + 1) * 8) != hipSuccess) {
-    set_error(-1, "rows: device allocation failed");
-    return done();
-  }
-  if (hipMemcpyAsync(d_keys, keys, n * sizeof(kg_set), hipMemcpyHostToDevice, stream) != hipSuccess) return done();
+  if (d_keys.reserve(n) || d_node.reserve(n) || d_len.reserve(n + 1)) return set_error(-1, "rows: device allocation failed");
+  if (hipMemcpyAsync(d_keys, keys, n * sizeof(kg_set), hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_rows_find, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, ds, d_keys, (uint32_t)n,
                      d_node, d_len);
   if (hipMemcpyAsync(len.data(), d_len, n * 8, hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess) {
-    set_error(-1, "rows: lookup failed");
-    return done();
+    return set_error(-1, "rows: lookup failed");
   }
   for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + len[i];
   const uint64_t total = offsets[n];
-  rc = (int64_t)total;
-  if (!out || !total) return done();
-  if (cap < total) {
-    rc = set_error(-3, "rows buffer too small (%llu < %llu)", (unsigned long long)cap, (unsigned long long)total);
-    return done();
-  }
-  rc = -1;
-  if (hipMalloc(&d_out, total * sizeof(kg_tuple)) != hipSuccess) {
-    set_error(-1, "rows: device allocation failed");
-    return done();
-  }
+  if (!out || !total) return (int64_t)total;
+  if (cap < total)
+    return set_error(-3, "rows buffer too small (%llu < %llu)", (unsigned long long)cap, (unsigned long long)total);
+  if (d_out.reserve(total)) return set_error(-1, "rows: device allocation failed");
   // d_len now holds the offsets
-  if (hipMemcpyAsync(d_len, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess) return done();
+  if (hipMemcpyAsync(d_len, offsets, (n + 1) * 8, hipMemcpyHostToDevice, stream) != hipSuccess) return -1;
   hipLaunchKernelGGL(k_rows_fill, dim3((uint32_t)((n * 64 + 255) / 256)), dim3(256), 0, stream, ds, d_node, d_len,
                      (uint32_t)n, d_out);
   if (hipMemcpyAsync(out, d_out, total * sizeof(kg_tuple), hipMemcpyDeviceToHost, stream) != hipSuccess ||
       hipStreamSynchronize(stream) != hipSuccess) {
-    set_error(-1, "rows: copy failed");
-    return done();
+    return set_error(-1, "rows: copy failed");
   }
-  rc = (int64_t)total;
-  return done();
+  return (int64_t)total;
 }
 
 }  // namespace kg

@@ -1024,13 +1024,7 @@ __global__ void k_shard_finish(uint32_t n, uint8_t* res, uint32_t* err, ShardFor
 static int shard_formula(Snapshot* s, ShardCtx* c, size_t n, ShardFormula* F) {
   *F = ShardFormula{nullptr, nullptr, 0, s->d_virt, nullptr};
   if (!s->n_fplans) return 0;
-  if (n > c->ref_n) {
-    if (c->ref) HIPC(hipFree(c->ref));
-    c->ref = nullptr;
-    c->ref_n = 0;
-    HIPC(hipMalloc((void**)&c->ref, std::max<size_t>(n, 1024) * 4));
-    c->ref_n = std::max<size_t>(n, 1024);
-  }
+  if (n > c->ref.cap()) HIPC(c->ref.reserve(std::max<size_t>(n, 1024)));
   *F = ShardFormula{s->d_fidx, (const FPlan*)s->d_fplans, 1 + s->fp_leaves, s->d_virt, c->ref};
   return 0;
 }
@@ -1057,15 +1051,14 @@ int shard_bad_nodes(Snapshot* s, uint64_t* count) {
   HIPC(hipSetDevice(s->device));
   *count = 0;
   if (!s->ds.n_nodes) return 0;
-  unsigned long long* d = nullptr;
-  HIPC(hipMalloc((void**)&d, 8));
+  DevBuf<unsigned long long> d;
+  HIPC(d.reserve(1));
   HIPC(hipMemsetAsync(d, 0, 8, s->stream));
   hipLaunchKernelGGL(k_shard_bad_nodes, dim3((s->ds.n_nodes + 255) / 256), dim3(256), 0, s->stream, s->ds, d);
   HIPC(hipGetLastError());
   unsigned long long h = 0;
   HIPC(hipMemcpyAsync(&h, d, 8, hipMemcpyDeviceToHost, s->stream));
   HIPC(hipStreamSynchronize(s->stream));
-  HIPC(hipFree(d));
   *count = h;
   return 0;
 }
@@ -1159,24 +1152,17 @@ static int shard_vis_prepare(Snapshot* s, ShardCtx* c, hipStream_t stream, size_
   // default 2^23 = 64 MiB); an overflow is reported in the flags and the driver grows it
   (void)n;
   const uint64_t slots = 1ull << s->shard_vis_log2;
-  if (c->vis && c->vis_slots != slots) {
-    HIPC(hipFree(c->vis));
-    c->vis = nullptr;
-  }
-  if (!c->vis) {
-    HIPC(hipMalloc(&c->vis, slots * 8));
-    c->vis_slots = slots;
-  }
+  if (c->vis_slots != slots) c->vis.reset();
+  HIPC(c->vis.reserve(slots));
+  c->vis_slots = slots;
   HIPC(hipMemsetAsync(c->vis, 0xFF, c->vis_slots * 8, stream));
-  if (!c->heavy) {
-    HIPC(hipMalloc(&c->heavy, (size_t)SHARD_HEAVY_CAP * sizeof(HeavyRow) + 256 + HEAVY_TF_CAP * 4));
-  }
+  HIPC(c->heavy.reserve((size_t)SHARD_HEAVY_CAP * sizeof(HeavyRow) + 256 + HEAVY_TF_CAP * 4));
   return 0;
 }
 
 // The stream's hub-row list: rows, then the packed counter, then the tile map.
 static HeavyList heavy_list(ShardCtx* c) {
-  HeavyRow* rows = (HeavyRow*)c->heavy;
+  HeavyRow* rows = (HeavyRow*)c->heavy.get();
   unsigned long long* pk = (unsigned long long*)(rows + SHARD_HEAVY_CAP);
   uint32_t* tf = (uint32_t*)((char*)pk + 256);
   return HeavyList{rows, pk, tf, SHARD_HEAVY_CAP};
@@ -1201,16 +1187,10 @@ int shard_seed(Snapshot* s, const kg_query* d_q, size_t n, int32_t gdepth, kg_fr
   c->gdepth = gdepth;
   uint4* qinfo = nullptr;
   if (shard_escalates(s)) {
-    if (!c->qcnt) HIPC(hipMalloc(&c->qcnt, (4ull << QCNT_LOG2)));
+    HIPC(c->qcnt.reserve(1ull << QCNT_LOG2));
     HIPC(hipMemsetAsync(c->qcnt, 0, (4ull << QCNT_LOG2), stream));
-    if (slots > c->qinfo_n) {
-      if (c->qinfo) HIPC(hipFree(c->qinfo));
-      c->qinfo = nullptr;
-      c->qinfo_n = 0;
-      HIPC(hipMalloc(&c->qinfo, std::max<size_t>(slots, 1024) * sizeof(uint4)));
-      c->qinfo_n = std::max<size_t>(slots, 1024);
-    }
-    qinfo = (uint4*)c->qinfo;
+    if (slots > c->qinfo.cap()) HIPC(c->qinfo.reserve(std::max<size_t>(slots, 1024)));
+    qinfo = c->qinfo;
     if (slots > n) HIPC(hipMemsetAsync(qinfo + n, 0, (slots - n) * sizeof(uint4), stream));
   }
   ShardFormula F;
@@ -1279,13 +1259,7 @@ int shard_levels(Snapshot* s, int levels, kg_frec* d_buf[2], size_t cap, uint32_
   ShardCtx* c = s->shard_ctx(stream);
   if (!c || !c->vis) return set_error(-2, "kg_shard_levels before kg_shard_seed (on this stream)");
   const uint32_t words = (uint32_t)((slots + 31) / 32);
-  if ((size_t)words + 1 > c->bits_n) {
-    if (c->bits) HIPC(hipFree(c->bits));
-    c->bits = nullptr;
-    c->bits_n = 0;
-    HIPC(hipMalloc((void**)&c->bits, ((size_t)words + 1) * 4));
-    c->bits_n = (size_t)words + 1;
-  }
+  HIPC(c->bits.reserve((size_t)words + 1));
   const HeavyList heavy = heavy_list(c);
   const uint32_t esc = esc_mode == 1 ? ESC_BIT : (esc_mode == 2 ? ESC2_BIT : 0u);
   const uint32_t budget = shard_escalates(s) && c->qcnt && !c->final ? s->shard_budget : 0u;
@@ -1294,7 +1268,7 @@ int shard_levels(Snapshot* s, int levels, kg_frec* d_buf[2], size_t cap, uint32_
   // sub mode): level 0 reads the seed's bucket, every later level the SUB segments of the one before
   const uint32_t SUB = cap >= 8 * 256 ? 8u : 1u;
   const uint64_t seg = cap / SUB;
-  if (!c->cnt8) HIPC(hipMalloc((void**)&c->cnt8, 32 * 4));
+  HIPC(c->cnt8.reserve(32));
   HIPC(hipMemsetAsync(c->cnt8, 0, 32 * 4, stream));
   uint32_t* sub[2] = {c->cnt8, c->cnt8 + 16};
   uint32_t* maxsub = c->cnt8 + 12;  // the largest sub-bucket count of any level (k_shard_heavy / _prep)
@@ -1366,7 +1340,7 @@ int shard_back_list(Snapshot* s, size_t n, const uint8_t* d_res, const uint32_t*
   if (!c->vis) return set_error(-2, "kg_shard_back_list before kg_shard_seed");
   HIPC(hipMemsetAsync(c->vis, 0xFF, c->vis_slots * 8, stream));  // backward keys start clear
   if (c->qcnt) HIPC(hipMemsetAsync(c->qcnt, 0, (4ull << QCNT_LOG2), stream));  // reverse-edge counts
-  if (n && shard_escalates(s) && c->qinfo && n <= c->qinfo_n) {
+  if (n && shard_escalates(s) && c->qinfo && n <= c->qinfo.cap()) {
     hipLaunchKernelGGL(k_shard_back_list, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, (uint32_t)n, d_res,
                        d_err, (const uint4*)c->qinfo, s->shard_rank, d_list, (uint64_t)cap, d_counts);
     HIPC(hipGetLastError());
@@ -1384,7 +1358,7 @@ int shard_refwd_seed(Snapshot* s, size_t n, const uint8_t* d_res, const uint32_t
   if (!c->vis) return set_error(-2, "kg_shard_refwd_seed before kg_shard_seed");
   HIPC(hipMemsetAsync(c->vis, 0xFF, c->vis_slots * 8, stream));  // forward keys start clear again
   c->final = true;  // kg_shard_level runs without escalation until the next kg_shard_seed
-  if (n && shard_escalates(s) && c->qinfo && n <= c->qinfo_n) {
+  if (n && shard_escalates(s) && c->qinfo && n <= c->qinfo.cap()) {
     hipLaunchKernelGGL(k_shard_refwd_seed, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, stream, s->ds, (uint32_t)n,
                        d_res, d_err, (const uint4*)c->qinfo, d_out, (uint64_t)cap, d_counts);
     HIPC(hipGetLastError());

@@ -47,23 +47,17 @@ struct ShardComm {
   std::mutex mu;
   bool prune = false;
   // device buffers, grown on demand
-  kg_frec* buf[2] = {nullptr, nullptr};
-  kg_frec* recv = nullptr;
+  DevBuf<kg_frec> buf[2], recv;
   size_t recs = 0;                  // records each of buf[0], buf[1], recv holds (N * B)
-  uint32_t* cnt = nullptr;          // counts[2][N + 1] | rc[N]
-  unsigned long long* acc = nullptr;  // acc[4] | tot[8] | scratch[8]
-  uint32_t* bits = nullptr;
-  uint32_t* bits_all = nullptr;
-  size_t words_cap = 0, all_cap = 0;
-  uint8_t* res = nullptr;
-  uint32_t* err = nullptr;
-  size_t slots_cap = 0;
-  kg_query* dq = nullptr;  // kg_check_batch (host buffers): staged queries and results
-  uint8_t* dout = nullptr;
-  uint32_t* derr = nullptr;
-  size_t dq_cap = 0;
-  void* pinned = nullptr;  // host staging: host-memory transports and readbacks
-  size_t pinned_bytes = 0;
+  DevBuf<uint32_t> cnt;             // counts[2][N + 1] | rc[N]
+  DevBuf<unsigned long long> acc;   // acc[4] | tot[8] | scratch[8]
+  DevBuf<uint32_t> bits, bits_all;
+  DevBuf<uint8_t> res;
+  DevBuf<uint32_t> err;  // allocated after res: its capacity is the result slots both hold
+  DevBuf<kg_query> dq;   // kg_check_batch (host buffers): staged queries and results
+  DevBuf<uint8_t> dout;
+  DevBuf<uint32_t> derr;  // allocated last of the three: its capacity is the queries all hold
+  PinBuf<void> pinned;    // host staging: host-memory transports and readbacks
   size_t bucket = 0;     // one rank's device loop: B, learned from the previous batch
   // the exchange protocol: B_k records per destination for exchange k (k = 0 .. gdepth; the seed
   // writes exchange 0's buckets, level k - 1 exchange k's), each learned from the largest bucket
@@ -71,8 +65,7 @@ struct ShardComm {
   // destination of exchange k gets B_k records on the wire whatever it holds
   std::vector<size_t> lb;
   size_t bb = 0;  // escalation: records per rank of a backward-phase all-gather, learned like B_k
-  unsigned long long* red = nullptr;  // [8 + levels]: the end-of-batch all-reduce (tot[5] | per-exchange largest)
-  size_t red_cap = 0;
+  DevBuf<unsigned long long> red;  // [8 + levels]: the end-of-batch all-reduce (tot[5] | per-exchange largest)
   std::vector<uint64_t> lvl_last, lb_last;  // the last batch: per exchange its largest bucket and B_k
   // exchanges a batch runs (round 6): learned from the last batch -- its last
   // non-empty exchange + 2 -- instead of always gdepth + 1 (the trailing ones carried nothing and cost
@@ -86,26 +79,13 @@ struct ShardComm {
 };
 
 ShardComm::~ShardComm() {
-  if (device >= 0) hipSetDevice(device);
-  if (run) hipStreamSynchronize(run);
-  if (nccl) ncclCommDestroy(nccl);
+  // the stream is idle and the communicator gone before any buffer is freed (the members, after this body)
+  if (device >= 0) (void)hipSetDevice(device);
+  if (run) (void)hipStreamSynchronize(run);
+  if (nccl) (void)ncclCommDestroy(nccl);
   if (xbufs) expand_bufs_free(xbufs);
-  hipFree(buf[0]);
-  hipFree(buf[1]);
-  hipFree(recv);
-  hipFree(cnt);
-  hipFree(acc);
-  hipFree(red);
-  hipFree(bits);
-  hipFree(bits_all);
-  hipFree(res);
-  hipFree(err);
-  hipFree(dq);
-  hipFree(dout);
-  hipFree(derr);
-  if (pinned) hipHostFree(pinned);
   for (auto e : ev)
-    if (e) hipEventDestroy(e);
+    if (e) (void)hipEventDestroy(e);
 }
 
 void shard_comms_free(Snapshot* s) {
@@ -169,14 +149,7 @@ static int rccl_allreduce_max(void* ctx, uint64_t* buf, size_t count, void* stre
 
 // ------------------------------------------------------------------ transport calls, staged as needed
 static void* pinned_at_least(ShardComm* c, size_t bytes) {
-  if (bytes > c->pinned_bytes) {
-    if (c->pinned) hipHostFree(c->pinned);
-    c->pinned = nullptr;
-    c->pinned_bytes = 0;
-    const size_t b = std::max<size_t>(bytes, 1 << 16);
-    if (hipHostMalloc(&c->pinned, b) != hipSuccess) return nullptr;
-    c->pinned_bytes = b;
-  }
+  if (bytes > c->pinned.cap() && c->pinned.reserve(std::max<size_t>(bytes, 1 << 16))) return nullptr;
   return c->pinned;
 }
 
@@ -243,8 +216,8 @@ static int h_alltoall2(ShardComm* c, const void* s0, void* r0, size_t b0, const 
     return tcall(c->t.alltoall2(c->t.ctx, s0, r0, b0, s1, r1, b1, nullptr), "alltoall2");
   }
   const size_t N = (size_t)c->world, a = N * b0, b = N * b1;
-  char* d = nullptr;
-  HIPC(hipMalloc(&d, 2 * (a + b) + 16));
+  DevBuf<char> d;
+  HIPC(d.reserve(2 * (a + b) + 16));
   int rc = 0;
   if (a) rc |= hipMemcpyAsync(d, s0, a, hipMemcpyHostToDevice, c->run) != hipSuccess;
   if (b) rc |= hipMemcpyAsync(d + a, s1, b, hipMemcpyHostToDevice, c->run) != hipSuccess;
@@ -253,7 +226,6 @@ static int h_alltoall2(ShardComm* c, const void* s0, void* r0, size_t b0, const 
   if (!rc && a && hipMemcpyAsync(r0, d + a + b, a, hipMemcpyDeviceToHost, c->run) != hipSuccess) rc = -1;
   if (!rc && b && hipMemcpyAsync(r1, d + 2 * a + b, b, hipMemcpyDeviceToHost, c->run) != hipSuccess) rc = -1;
   if (hipStreamSynchronize(c->run) != hipSuccess && !rc) rc = set_error(-1, "D2H staging");
-  hipFree(d);
   return rc;
 }
 
@@ -366,23 +338,12 @@ __global__ void k_sc_or(const uint32_t* __restrict__ parts, uint32_t N, uint64_t
 }
 
 // ------------------------------------------------------------------ binding
-static int grow(void** p, size_t* have, size_t want, size_t unit) {
-  if (want <= *have && *p) return 0;
-  if (*p) hipFree(*p);
-  *p = nullptr;
-  *have = 0;
-  const size_t n = std::max<size_t>(want, 1024);
-  HIPC(hipMalloc(p, n * unit));
-  *have = n;
-  return 0;
-}
-
 // Collective, once per binding: the OR of every rank's holder bitmap (kg_shard_seed's no-holder test
 // across ranks) and whether any rank can end a check in an error (pruning through the done bitmap).
 static int comm_setup(Snapshot* s, ShardComm* c) {
-  HIPC(hipMalloc((void**)&c->acc, 32 * 8));
+  HIPC(c->acc.reserve(32));
   HIPC(hipMemsetAsync(c->acc, 0, 32 * 8, c->run));
-  HIPC(hipMalloc((void**)&c->cnt, (4 * (size_t)KG_SHARD_MAX_RANKS + 8) * 4));
+  HIPC(c->cnt.reserve(4 * (size_t)KG_SHARD_MAX_RANKS + 8));
   uint64_t bad = 0;
   if (int rc = shard_bad_nodes(s, &bad)) return rc;
   size_t words = 0;
@@ -390,49 +351,31 @@ static int comm_setup(Snapshot* s, ShardComm* c) {
   // remote child metadata (DevSnap::remote_meta) runs when every rank wants it (not yet done, knob on)
   // and every rank has the same node id space (node ids are global: kg_snapshot.hip create_from_tuples)
   const uint64_t nn = s->ds.n_nodes;
-  uint64_t* dmeta = nullptr;  // allocated before the agreement: a rank without it makes every rank skip
-  if (c->world > 1 && !s->ds.remote_meta && s->shard_remote_meta && nn &&
-      hipMalloc((void**)&dmeta, nn * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    dmeta = nullptr;
-  }
+  DevBuf<uint64_t> dmeta;  // allocated before the agreement: a rank without it makes every rank skip
+  if (c->world > 1 && !s->ds.remote_meta && s->shard_remote_meta && nn && dmeta.reserve(nn)) (void)hipGetLastError();
   // a host-memory transport stages the all-reduce through pinned memory: taken now, so a rank that
   // cannot have it makes every rank skip instead of failing alone inside the collective below
-  if (dmeta && c->t.host_memory && !pinned_at_least(c, nn * 8)) {
-    hipFree(dmeta);
-    dmeta = nullptr;
-  }
+  if (dmeta && c->t.host_memory && !pinned_at_least(c, nn * 8)) dmeta.reset();
   const uint64_t skip = dmeta ? 0 : 1;
   uint64_t v[4] = {bad, words, nn, 0xFFFFFFFFull - nn};
   v[3] |= skip << 40;
-  if (int rc = h_allreduce_max(c, v, 4)) {
-    hipFree(dmeta);
-    return rc;
-  }
+  if (int rc = h_allreduce_max(c, v, 4)) return rc;
   c->prune = v[0] == 0;
   words = (size_t)v[1];
   const bool meta = !(v[3] >> 40) && v[2] == 0xFFFFFFFFull - (v[3] & 0xFFFFFFFFull);
-  if (!meta) {
-    hipFree(dmeta);
-    dmeta = nullptr;
-  }
+  if (!meta) dmeta.reset();
   if (c->world > 1 && words) {
-    uint32_t *mine = nullptr, *all = nullptr;
-    HIPC(hipMalloc((void**)&mine, words * 4));
-    HIPC(hipMalloc((void**)&all, (size_t)c->world * words * 4));
+    DevBuf<uint32_t> mine, all;
+    HIPC(mine.reserve(words));
+    HIPC(all.reserve((size_t)c->world * words));
     int rc = shard_held(s, mine, words, 0, c->run);
     if (!rc) rc = x_allgather(c, mine, all, words * 4);
     if (!rc) {
-      hipLaunchKernelGGL(k_sc_or, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, c->run, all, (uint32_t)c->world,
-                         (uint64_t)words, mine);
+      hipLaunchKernelGGL(k_sc_or, dim3((uint32_t)((words + 255) / 256)), dim3(256), 0, c->run, all.get(), (uint32_t)c->world,
+                         (uint64_t)words, mine.get());
       rc = shard_held(s, mine, words, 1, c->run);  // synchronises
     }
-    hipFree(mine);
-    hipFree(all);
-    if (rc) {
-      hipFree(dmeta);
-      return rc;
-    }
+    if (rc) return rc;
   }
   if (dmeta) {
     // one max all-reduce of 8 B per node: each node's (row length, signature) word is non-zero on its
@@ -440,7 +383,7 @@ static int comm_setup(Snapshot* s, ShardComm* c) {
     // step failed contributes zeros and a failure flag, and the second all-reduce makes every rank skip
     // the metadata together (the nowner path: more records, the same answers).  Only a failed
     // collective (the transport itself) or a failed apply on this rank fails the bind.
-    uint64_t* d = dmeta;
+    uint64_t* d = dmeta;  // (freed when this function returns)
     const int lrc = shard_meta_local(s, d, c->run);
     if (lrc && hipMemsetAsync(d, 0, nn * 8, c->run) != hipSuccess) (void)hipGetLastError();
     int rc = x_allreduce_max(c, reinterpret_cast<unsigned long long*>(d), nn);
@@ -448,7 +391,6 @@ static int comm_setup(Snapshot* s, ShardComm* c) {
     if (!rc) rc = h_allreduce_max(c, &failed, 1);
     if (!rc && !failed) rc = shard_meta_apply(s, d, c->run);  // synchronises
     else (void)hipStreamSynchronize(c->run);
-    hipFree(d);
     if (rc) return rc;
   }
   return 0;
@@ -482,18 +424,17 @@ static int bind(Snapshot* s, ShardComm* c, hipStream_t st) {
 // s->rel_span (1 + the largest relation id of any node; collective callers all compute their own)
 static int rel_span(Snapshot* s, hipStream_t st) {
   if (s->rel_span || !s->ds.n_nodes) return 0;
-  unsigned int* d = nullptr;
-  HIPC(hipMalloc((void**)&d, 4));
+  DevBuf<unsigned int> d;
+  HIPC(d.reserve(1));
   unsigned int h = 0;
   int rc = hipMemsetAsync(d, 0, 4, st) != hipSuccess;
   if (!rc) {
     const uint64_t nn = s->ds.n_nodes;
     hipLaunchKernelGGL(k_sc_rel_span, dim3((uint32_t)std::min<uint64_t>((nn + 255) / 256, 4096)), dim3(256), 0, st,
-                       s->ds.nd_rel, nn, d);
+                       s->ds.nd_rel, nn, d.get());
     rc = hipGetLastError() != hipSuccess || hipMemcpyAsync(&h, d, 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
          hipStreamSynchronize(st) != hipSuccess;
   }
-  hipFree(d);
   if (rc) return set_error(-1, "relation span of the snapshot's nodes");
   s->rel_span = std::max(h, 1u);
   return 0;
@@ -620,14 +561,12 @@ static int general_phase(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t 
   int rc = g->init_device(s->device);
   if (!rc) rc = g->create_from_tuples(region.data(), region.size(), &s->prog_copy.dict, prog ? &p : nullptr);
   const size_t m = open.size();
-  kg_query* dq = nullptr;
-  uint8_t* dout = nullptr;
-  uint32_t* derr = nullptr;
+  DevBuf<kg_query> dq;
+  DevBuf<uint8_t> dout;
+  DevBuf<uint32_t> derr;
   std::vector<uint8_t> r(m);
   std::vector<uint32_t> e(m);
-  if (!rc && (hipMalloc(&dq, m * sizeof(kg_query)) != hipSuccess || hipMalloc(&dout, m) != hipSuccess ||
-              hipMalloc(&derr, m * 4) != hipSuccess))
-    rc = set_error(-1, "general phase buffers");
+  if (!rc && (dq.reserve(m) || dout.reserve(m) || derr.reserve(m))) rc = set_error(-1, "general phase buffers");
   // everything on the region snapshot's own stream (non-blocking: the null stream would not wait for
   // it), completed before the results are read
   if (!rc && hipMemcpyAsync(dq, oq.data(), m * sizeof(kg_query), hipMemcpyHostToDevice, g->stream) != hipSuccess)
@@ -638,11 +577,9 @@ static int general_phase(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t 
               hipStreamSynchronize(g->stream) != hipSuccess))
     rc = set_error(-1, "general phase D2H");
   if (g->stream) (void)hipStreamSynchronize(g->stream);  // nothing of g's still running when it is freed
-  hipFree(dq);
-  hipFree(dout);
-  hipFree(derr);
+  dq.reset(), dout.reset(), derr.reset();  // before the region snapshot goes, as ever
   delete g;
-  hipSetDevice(s->device);
+  (void)hipSetDevice(s->device);
   if (rc) return rc;
   for (size_t k = 0; k < m; k++) {
     hres[open[k]] = r[k];
@@ -686,7 +623,7 @@ int shard_expand(Snapshot* s, const kg_set* roots, size_t n, int32_t gdepth, kg_
   if (!rc) rc = expand_batch(g, g->stream, &bufs, roots, n, gdepth, out);
   if (bufs) expand_bufs_free(bufs);
   delete g;
-  hipSetDevice(s->device);
+  (void)hipSetDevice(s->device);
   return rc;
 }
 
@@ -695,15 +632,10 @@ int shard_expand(Snapshot* s, const kg_set* roots, size_t n, int32_t gdepth, kg_
 // finds the same allocation state on all of them (allocation decisions stay symmetric: a rank that
 // allocates alone would wait in the all-reduce below for ranks that never get there).
 static void drop_buffers(ShardComm* c) {
-  for (kg_frec** p : {&c->buf[0], &c->buf[1], &c->recv}) {
-    hipFree(*p);
-    *p = nullptr;
-  }
+  for (auto* b : {&c->buf[0], &c->buf[1], &c->recv}) b->reset();
   c->recs = 0;
-  hipFree(c->bits);
-  hipFree(c->bits_all);
-  c->bits = c->bits_all = nullptr;
-  c->words_cap = c->all_cap = 0;
+  c->bits.reset();
+  c->bits_all.reset();
 }
 
 // Bucket buffers may take this much (kg_snapshot_tune "shard_max_bytes"; default a quarter of the free
@@ -720,25 +652,23 @@ static uint64_t bucket_byte_cap(const Snapshot* s, const ShardComm* c) {
 // any rank -- a cap or an out-of-memory -- is returned by all of them.
 static int grow_run(Snapshot* s, ShardComm* c, bool xch, size_t B, uint32_t words) {
   const size_t N = (size_t)c->world;
-  const bool g_bits = !c->bits || !c->bits_all || (size_t)words + 1 > c->words_cap || N * words + 1 > c->all_cap;
-  const bool g_recs = N * B > c->recs || !c->buf[0];
+  const bool g_bits =
+      c->bits.empty() || c->bits_all.empty() || (size_t)words + 1 > c->bits.cap() || N * words + 1 > c->bits_all.cap();
+  const bool g_recs = N * B > c->recs || c->buf[0].empty();
   if (!g_bits && !g_recs) return 0;
   uint64_t f = 0;
   const uint64_t bytes = 3ull * N * B * sizeof(kg_frec), cap = bucket_byte_cap(s, c);
   if (g_recs) {
-    for (kg_frec** p : {&c->buf[0], &c->buf[1], &c->recv}) {
-      hipFree(*p);
-      *p = nullptr;
-    }
+    for (auto* b : {&c->buf[0], &c->buf[1], &c->recv}) b->reset();
     c->recs = 0;
     if (bytes > cap) f = 1;
-    for (kg_frec** p : {&c->buf[0], &c->buf[1], &c->recv})
-      if (!f && hipMalloc((void**)p, N * B * sizeof(kg_frec)) != hipSuccess) f = 2;
+    for (auto* b : {&c->buf[0], &c->buf[1], &c->recv})
+      if (!f && b->reserve(N * B)) f = 2;
     if (!f) c->recs = N * B;
   }
   if (!f && g_bits &&
-      (grow((void**)&c->bits, &c->words_cap, (size_t)words + 1, 4) ||
-       grow((void**)&c->bits_all, &c->all_cap, N * words + 1, 4)))
+      (c->bits.reserve(std::max<size_t>((size_t)words + 1, 1024)) ||
+       c->bits_all.reserve(std::max<size_t>(N * words + 1, 1024))))
     f = 2;
   const uint64_t mine = f;
   if (xch) {
@@ -791,15 +721,10 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
   // without the exchange needs none).
   const size_t slots = shard_result_slots(s, n);
   uint64_t bad = (n > 0x7FFFFFFFull || slots > shard_slot_limit()) ? 1 : 0;
-  if (!bad && (slots > c->slots_cap || !c->res)) {
-    hipFree(c->res);
-    hipFree(c->err);
-    c->res = nullptr;
-    c->err = nullptr;
-    c->slots_cap = 0;
+  if (!bad && (slots > c->err.cap() || c->res.empty())) {
+    c->res.reset(), c->err.reset();
     const size_t m = std::max<size_t>(slots, 1024);
-    if (hipMalloc((void**)&c->res, m) != hipSuccess || hipMalloc((void**)&c->err, m * 4) != hipSuccess) bad = 2;
-    else c->slots_cap = m;
+    if (c->res.reserve(m) || c->err.reserve(m)) bad = 2;
   }
   uint64_t agree[2] = {slots, bad};
   if (xch) {
@@ -818,20 +743,15 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
   // exchanges k = 0 .. L - 1 (L = gdepth + 1); lb[L] bounds what the last level emits (nothing)
   const int L = gdepth + 1;
   if (xch && (int)c->lb.size() != L + 1) c->lb.assign((size_t)L + 1, c->bucket ? c->bucket : B0);
-  if (xch && c->red_cap < (size_t)(8 + L)) {
-    hipFree(c->red);
-    c->red = nullptr;
-    c->red_cap = 0;
-    uint64_t f = hipMalloc((void**)&c->red, (size_t)(8 + L) * 8) != hipSuccess ? 1 : 0;
+  if (xch && c->red.cap() < (size_t)(8 + L)) {
+    uint64_t f = c->red.reserve((size_t)(8 + L)) ? 1 : 0;
     const uint64_t mine = f;
     if (int rc = h_allreduce_max(c, &f, 1)) return rc;
     c->st[2]++;
     if (f) {
-      hipFree(c->red);
-      c->red = nullptr;
+      c->red.reset();
       return set_error(KG_ERR_RESOURCE_CODE, "sharded batch: reduction buffer (%s)", mine ? "this rank" : "another rank");
     }
-    c->red_cap = (size_t)(8 + L);
   }
   uint32_t* counts[2] = {c->cnt, c->cnt + (N + 1)};
   uint32_t* rcv = c->cnt + 2 * (N + 1);
@@ -1095,19 +1015,12 @@ static int shard_check_host(Snapshot* s, ShardComm* c, const kg_query* q, size_t
   {
     std::lock_guard<std::mutex> lk(c->mu);
     HIPC(hipSetDevice(s->device));
-    if (n > c->dq_cap || !c->dq) {
-      hipFree(c->dq);
-      hipFree(c->dout);
-      hipFree(c->derr);
-      c->dq = nullptr;
-      c->dout = nullptr;
-      c->derr = nullptr;
-      c->dq_cap = 0;
+    if (n > c->derr.cap() || c->dq.empty()) {
+      c->dq.reset(), c->dout.reset(), c->derr.reset();
       const size_t m = std::max<size_t>(n, 1024);
-      HIPC(hipMalloc((void**)&c->dq, m * sizeof(kg_query)));
-      HIPC(hipMalloc((void**)&c->dout, m));
-      HIPC(hipMalloc((void**)&c->derr, m * 4));
-      c->dq_cap = m;
+      HIPC(c->dq.reserve(m));
+      HIPC(c->dout.reserve(m));
+      HIPC(c->derr.reserve(m));
     }
     if (n) HIPC(hipMemcpyAsync(c->dq, q, n * sizeof(kg_query), hipMemcpyHostToDevice, c->run));
   }

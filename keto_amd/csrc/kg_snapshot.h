@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <list>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/ketogpu.h"
+#include "kg_buf.h"
 #include "kg_grid.h"
 #include "kg_internal.h"
 #include "kg_synth.h"
@@ -25,15 +27,39 @@ void clear_error();
 
 #define HIPC(expr)                                                                               \
   do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
+    hipError_t _e = (hipError_t)(expr); /* hipError_t, or a Buf::reserve's int */              \
     if (_e != hipSuccess) return ::kg::set_error(-1, "%s: %s (%s:%d)", #expr, hipGetErrorString(_e), \
                                                  __FILE__, __LINE__);                            \
   } while (0)
 
+// The two memories of kg_buf.h's Buf and BlockPool.  A buffer does not remember its device: owners set
+// it before they allocate and in their destructor's body (which runs before the members are freed).
+struct DeviceMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+  static void free(void* p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+  static int alloc(void** p, size_t bytes) { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = Buf<T, DeviceMem>;
+template <class T> using PinBuf = Buf<T, PinnedMem>;
+
+// The device temporaries of one build function: freed together when it returns, on every path.
+struct DevTemps {
+  std::vector<DevBuf<void>> bufs;
+  int alloc(void** p, size_t bytes) {
+    DevBuf<void> b;
+    HIPC(b.reserve(std::max<size_t>(bytes, 16)));
+    *p = b.get();
+    bufs.push_back(std::move(b));
+    return 0;
+  }
+};
+
 // Grid-tier memory (kg_grid.hip): visited hash | entry log | tile maps | slots | control block.
 struct GridPool {
-  void* mem = nullptr;
-  size_t bytes = 0;
+  DevBuf<void> mem;  // cap(): bytes
   uint64_t cap = 0;    // log entries the pool is laid out for (0: not yet)
   uint32_t epoch = 0;  // visited-table epoch of the last round
   void release();
@@ -47,16 +73,13 @@ struct Workspace {
   int device = -1;
   hipStream_t stream = nullptr;
   std::mutex mu;
-  void* scratch = nullptr;
-  size_t scratch_bytes = 0;
+  DevBuf<void> scratch;  // cap(): bytes
   size_t scratch_n = 0;  // queries the scratch was last sized for
   GridPool grid;  // grid tier, sized for the queries that reach it (16 Mi log entries)
   GridPool ms;    // the grid tier's MS-BFS path (kg_msbfs.hip): dense masks of its query groups
   bool grid_reran = false;  // the last batch's grid tier ran rounds after the first (results rewritten)
-  void* split = nullptr;  // formula split (kg_formula.hip): leaf queries, their results, per-query plan refs
-  size_t split_bytes = 0;
-  void* interp_pool = nullptr;
-  size_t interp_pool_bytes = 0;
+  DevBuf<void> split;  // formula split (kg_formula.hip): leaf queries, their results, per-query plan refs
+  DevBuf<void> interp_pool;
   uint64_t interp_layout = 0;  // (pass-2 slots, pass-1 slots, list cap) the pool was last laid out for
   hipEvent_t ev[6] = {};  // batch timing events (created on first use)
   // tail-tier level launches (k_grid_level / k_ms_level) of a batch with stats: one event pair each,
@@ -85,9 +108,8 @@ struct Workspace {
   hipEvent_t sync_ev = nullptr;  // blocking-sync event (host-buffer batches wait on it asleep)
   int wait(hipStream_t st, bool blocking);  // waits for st: spin (hipStreamSynchronize) or asleep
   void* exp = nullptr;  // expand buffers of kg_expand_batch_device calls on this stream (kg_expand.hip)
-  void* pinned = nullptr;  // 64 KiB of pinned host memory for small device->host readbacks
-  kg_query* unpacked = nullptr;  // packed device batches that need the original queries (a program)
-  size_t unpacked_n = 0;
+  PinBuf<void> pinned;  // 64 KiB of pinned host memory for small device->host readbacks
+  DevBuf<kg_query> unpacked;  // packed device batches that need the original queries (a program)
   void* host_buf(size_t bytes);
   ~Workspace();
 };
@@ -164,18 +186,15 @@ struct HostMap {
 struct ShardCtx {
   hipStream_t stream = nullptr;
   int device = -1;
-  void* vis = nullptr;  // per-batch visited table of (query, node)
+  DevBuf<uint64_t> vis;  // per-batch visited table of (query, node)
   uint64_t vis_slots = 0;
-  void* heavy = nullptr;  // hub rows a level hands to k_shard_heavy (+ count)
-  void* qcnt = nullptr;   // per-batch escalation counters (hashed by query)
-  void* qinfo = nullptr;  // per query slot (root, subject, depth, seeded)
-  size_t qinfo_n = 0;
+  DevBuf<void> heavy;     // hub rows a level hands to k_shard_heavy (+ count)
+  DevBuf<uint32_t> qcnt;  // per-batch escalation counters (hashed by query)
+  DevBuf<uint4> qinfo;    // per query slot (root, subject, depth, seeded)
   bool final = false;      // the batch's final forward phase (kg_shard_refwd_seed): no escalation
-  uint32_t* ref = nullptr;  // formula split: plan of every query of the batch
-  size_t ref_n = 0;
-  uint32_t* bits = nullptr;  // kg_shard_levels: the batch's done bitmap
-  size_t bits_n = 0;
-  uint32_t* cnt8 = nullptr;  // kg_shard_levels: per-XCD sub-bucket counters of the two level buffers (+ flags)
+  DevBuf<uint32_t> ref;   // formula split: plan of every query of the batch
+  DevBuf<uint32_t> bits;  // kg_shard_levels: the batch's done bitmap
+  DevBuf<uint32_t> cnt8;  // kg_shard_levels: per-XCD sub-bucket counters of the two level buffers (+ flags)
   int32_t gdepth = 0;        // the batch's global depth (kg_shard_seed): packed records need depths < 256
   ~ShardCtx();
 };
@@ -219,19 +238,18 @@ struct Lane {
   int device = -1;
   hipStream_t stream = nullptr;
   Workspace* w = nullptr;
-  kg_query* h_q = nullptr;
-  uint8_t* h_out = nullptr;
-  uint32_t* h_err = nullptr;
-  kg_query* d_q = nullptr;
-  uint8_t* d_out = nullptr;
-  uint32_t* d_err = nullptr;
-  size_t cap = 0;
+  PinBuf<kg_query> h_q;
+  PinBuf<uint8_t> h_out;
+  PinBuf<uint32_t> h_err;
+  DevBuf<kg_query> d_q;
+  DevBuf<uint8_t> d_out;
+  DevBuf<uint32_t> d_err;
+  size_t cap = 0;  // queries the six above hold
   void* exp = nullptr;  // expand buffers of this lane (kg_expand.hip)
   // kg_check_batch_packed: packed queries on the device (staged through h_q) and the error list
-  kg_query_packed* d_pk = nullptr;
-  uint32_t* d_el = nullptr;  // count word, pad, then (index, code) pairs: room for every query of the chunk
-  uint32_t* h_el = nullptr;  // pinned: the count and the first EL_PREFETCH pairs, read back with the answers
-  size_t pk_cap = 0;
+  DevBuf<kg_query_packed> d_pk;
+  DevBuf<uint32_t> d_el;  // count word, pad, then (index, code) pairs: room for every query of the chunk
+  PinBuf<uint32_t> h_el;  // pinned: the count and the first EL_PREFETCH pairs, read back with the answers
   static constexpr size_t EL_PREFETCH = 4096;
   int reserve(size_t n);
   int reserve_packed(size_t n);

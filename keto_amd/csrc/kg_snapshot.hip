@@ -291,18 +291,16 @@ Snapshot::~Snapshot() {
   for (auto& set : lane_sets)
     for (Lane* l : set) delete l;  // before the workspaces: a lane's stream owns one of them
   for (Snapshot* p : peers) delete p;
-  if (device >= 0) hipSetDevice(device);
-  for (auto& a : allocs) hipFree(a.first);
+  if (device >= 0) (void)hipSetDevice(device);
+  for (auto& a : allocs) (void)hipFree(a.first);
   for (Workspace* w : wss) delete w;
   for (ShardCtx* c : shard_ctxs) delete c;
   giant.release();
-  if (stream) hipStreamDestroy(stream);
+  if (stream) (void)hipStreamDestroy(stream);
 }
 
 void GridPool::release() {
-  if (mem) hipFree(mem);
-  mem = nullptr;
-  bytes = 0;
+  mem.reset();
   cap = 0;
   epoch = 0;
 }
@@ -323,42 +321,30 @@ int Workspace::wait(hipStream_t st, bool blocking) {
 }
 
 Workspace::~Workspace() {
-  if (device >= 0) hipSetDevice(device);
-  if (sync_ev) hipEventDestroy(sync_ev);
-  if (scratch) hipFree(scratch);
-  grid.release();
-  ms.release();
-  if (interp_pool) hipFree(interp_pool);
-  if (split) hipFree(split);
-  if (unpacked) hipFree(unpacked);
-  if (pinned) hipHostFree(pinned);
+  if (device >= 0) (void)hipSetDevice(device);
+  if (sync_ev) (void)hipEventDestroy(sync_ev);
   for (auto& e : ev)
-    if (e) hipEventDestroy(e);
+    if (e) (void)hipEventDestroy(e);
   for (auto& e : lev_ev)
-    if (e) hipEventDestroy(e);
+    if (e) (void)hipEventDestroy(e);
   if (exp) expand_bufs_free(exp);
 }
 
 void* Workspace::host_buf(size_t bytes) {
   if (bytes > 65536) return nullptr;
-  if (!pinned && hipHostMalloc(&pinned, 65536, hipHostMallocDefault) != hipSuccess) pinned = nullptr;
-  return pinned;
+  (void)pinned.reserve(65536);  // nullptr when the allocation fails
+  return pinned.get();
 }
 
 Lane::~Lane() {
-  if (device >= 0) hipSetDevice(device);
-  if (h_q) hipHostFree(h_q);
-  if (h_out) hipHostFree(h_out);
-  if (h_err) hipHostFree(h_err);
-  if (d_q) hipFree(d_q);
-  if (d_out) hipFree(d_out);
-  if (d_err) hipFree(d_err);
-  if (d_pk) hipFree(d_pk);
-  if (d_el) hipFree(d_el);
-  if (h_el) hipHostFree(h_el);
+  if (device >= 0) (void)hipSetDevice(device);
   if (exp) expand_bufs_free(exp);
-  // the stream's workspace belongs to the replica (freed with it); the stream itself is ours
-  if (stream) hipStreamDestroy(stream);
+  // the stream's workspace belongs to the replica (freed with it); the stream itself is ours -- synchronised
+  // here, where the frees used to do it, because the buffers are released after this body
+  if (stream) {
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
+  }
 }
 
 int Lane::reserve(size_t n) {
@@ -369,36 +355,28 @@ int Lane::reserve(size_t n) {
   size_t c = std::max<size_t>(n, 65536);
   c = std::max(c, 2 * cap);
   HIPC(hipStreamSynchronize(stream));
-  for (void* p : {(void*)h_q, (void*)h_out, (void*)h_err})
-    if (p) hipHostFree(p);
-  for (void* p : {(void*)d_q, (void*)d_out, (void*)d_err})
-    if (p) hipFree(p);
-  h_q = nullptr, h_out = nullptr, h_err = nullptr, d_q = nullptr, d_out = nullptr, d_err = nullptr;
+  // all six go before any comes back: the peak is the new set, not old + new
+  h_q.reset(), h_out.reset(), h_err.reset(), d_q.reset(), d_out.reset(), d_err.reset();
   cap = 0;
-  HIPC(hipHostMalloc(&h_q, c * sizeof(kg_query), hipHostMallocDefault));
-  HIPC(hipHostMalloc(&h_out, c, hipHostMallocDefault));
-  HIPC(hipHostMalloc(&h_err, c * 4, hipHostMallocDefault));
-  HIPC(hipMalloc(&d_q, c * sizeof(kg_query)));
-  HIPC(hipMalloc(&d_out, c));
-  HIPC(hipMalloc(&d_err, c * 4));
+  HIPC(h_q.reserve(c));
+  HIPC(h_out.reserve(c));
+  HIPC(h_err.reserve(c));
+  HIPC(d_q.reserve(c));
+  HIPC(d_out.reserve(c));
+  HIPC(d_err.reserve(c));
   cap = c;
   return 0;
 }
 
 int Lane::reserve_packed(size_t n) {
   if (int rc = reserve(n)) return rc;  // h_q stages the packed queries, d_q holds them unpacked
-  if (n <= pk_cap && d_pk) return 0;
+  if (n <= d_pk.cap() && !d_el.empty()) return 0;
   HIPC(hipSetDevice(device));
   HIPC(hipStreamSynchronize(stream));
-  if (d_pk) hipFree(d_pk);
-  if (d_el) hipFree(d_el);
-  d_pk = nullptr;
-  d_el = nullptr;
-  pk_cap = 0;
-  if (!h_el) HIPC(hipHostMalloc(&h_el, (2 + 2 * EL_PREFETCH) * 4, hipHostMallocDefault));
-  HIPC(hipMalloc(&d_pk, cap * sizeof(kg_query_packed)));
-  HIPC(hipMalloc(&d_el, (2 + 2 * cap) * 4));
-  pk_cap = cap;
+  d_pk.reset(), d_el.reset();
+  HIPC(h_el.reserve(2 + 2 * EL_PREFETCH));
+  HIPC(d_pk.reserve(cap));
+  HIPC(d_el.reserve(2 + 2 * cap));
   return 0;
 }
 
@@ -438,9 +416,7 @@ void Snapshot::lanes_release(std::vector<Lane*>* v) {
 }
 
 ShardCtx::~ShardCtx() {
-  if (device >= 0) hipSetDevice(device);
-  for (void* p : {vis, heavy, qcnt, qinfo, (void*)ref, (void*)bits, (void*)cnt8})
-    if (p) hipFree(p);
+  if (device >= 0) (void)hipSetDevice(device);
 }
 
 ShardCtx* Snapshot::shard_ctx(hipStream_t st, bool create) {
@@ -481,7 +457,7 @@ int Snapshot::alloc(void** p, size_t bytes) {
 void Snapshot::free_alloc(const void* p) {
   for (size_t i = 0; i < allocs.size(); i++)
     if (allocs[i].first == p) {
-      hipFree(allocs[i].first);
+      (void)hipFree(allocs[i].first);
       device_bytes -= allocs[i].second;
       allocs[i] = allocs.back();
       allocs.pop_back();
@@ -496,7 +472,7 @@ int Snapshot::init_device(int dev) {
   e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
   if (e != hipSuccess) return set_error(-1, "hipStreamCreate: %s", hipGetErrorString(e));
   int cus = 0;
-  hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 0;
   n_cu = cus > 0 ? cus : 256;
   return 0;
 }
@@ -509,8 +485,8 @@ int Snapshot::build_hash_tables() {
   if (alloc((void**)&adjx, (n_set_edges + 1) * sizeof(AdjX))) return -1;
   // per-node Bloom signature of the row subjects: inlined in adjx (child probes) and in the node map
   // (k_resolve's root probe)
-  uint2* sig = nullptr;
-  HIPC(hipMalloc(&sig, (size_t)ds.n_nodes * 8 + 8));
+  DevBuf<uint2> sig;
+  HIPC(sig.reserve((size_t)ds.n_nodes + 1));
   // direct tuples as checkDirect sees them: the check rows of a materialised snapshot, else the rows
   const uint64_t* coff = ds.crow_off ? ds.crow_off : ds.row_off;
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
@@ -525,14 +501,14 @@ int Snapshot::build_hash_tables() {
   if (hot) {
     const uint32_t nn = ds.n_nodes;
     if (alloc((void**)&xoff, ((size_t)nn + 1) * 4)) return -1;
-    unsigned long long* indeg = nullptr;
-    uint32_t *k0, *k1, *v0, *v1;
-    uint64_t *len, *pos;
-    HIPC(hipMalloc(&indeg, (size_t)nn * 8));
-    HIPC(hipMalloc(&k0, (size_t)nn * 4));
-    HIPC(hipMalloc(&k1, (size_t)nn * 4));
-    HIPC(hipMalloc(&v0, (size_t)nn * 4));
-    HIPC(hipMalloc(&v1, (size_t)nn * 4));
+    DevBuf<unsigned long long> indeg;
+    DevBuf<uint32_t> k0, k1, v0, v1;
+    DevBuf<uint64_t> len, pos;
+    HIPC(indeg.reserve(nn));
+    HIPC(k0.reserve(nn));
+    HIPC(k1.reserve(nn));
+    HIPC(v0.reserve(nn));
+    HIPC(v1.reserve(nn));
     HIPC(hipMemsetAsync(indeg, 0, (size_t)nn * 8, stream));
     hipLaunchKernelGGL(k_indeg, dim3(4096), dim3(256), 0, stream, ds.adj, n_set_edges, indeg);
     hipLaunchKernelGGL(k_hot_keys, dim3(4096), dim3(256), 0, stream, indeg, nn, k0, v0);
@@ -540,24 +516,23 @@ int Snapshot::build_hash_tables() {
     hipcub::DoubleBuffer<uint32_t> kb(k0, k1), vb(v0, v1);
     size_t tmp_bytes = 0;
     HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kb, vb, (size_t)nn, 0, 32, stream));
-    void* tmp = nullptr;
+    DevBuf<void> tmp;
     size_t scan_bytes = 0;
-    HIPC(hipFree(indeg));  // reuse its bytes: lengths and positions in sorted order (u64 each)
-    HIPC(hipMalloc(&len, ((size_t)nn + 1) * 8));
-    HIPC(hipMalloc(&pos, ((size_t)nn + 1) * 8));
-    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, len, pos, (size_t)nn, stream));
-    HIPC(hipMalloc(&tmp, std::max(tmp_bytes, scan_bytes) + 16));
+    indeg.reset();  // reuse its bytes: lengths and positions in sorted order (u64 each)
+    HIPC(len.reserve((size_t)nn + 1));
+    HIPC(pos.reserve((size_t)nn + 1));
+    HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, len.get(), pos.get(), (size_t)nn, stream));
+    HIPC(tmp.reserve(std::max(tmp_bytes, scan_bytes) + 16));
     HIPC(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kb, vb, (size_t)nn, 0, 32, stream));
     hipLaunchKernelGGL(k_hot_lens, dim3(4096), dim3(256), 0, stream, vb.Current(), ds.adj_off, nn, len);
     HIPC(hipGetLastError());
-    HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, len, pos, (size_t)nn, stream));
+    HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, scan_bytes, len.get(), pos.get(), (size_t)nn, stream));
     hipLaunchKernelGGL(k_hot_scatter, dim3(4096), dim3(256), 0, stream, vb.Current(), pos, nn, xoff);
     HIPC(hipGetLastError());
     HIPC(hipMemsetAsync(xoff + nn, 0, 4, stream));
     hipLaunchKernelGGL(k_build_adjx_hot, dim3(4096), dim3(256), 0, stream, ds.adj, ds.adj_off, xoff, sig, nn, adjx);
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(stream));
-    for (void* p : {(void*)k0, (void*)k1, (void*)v0, (void*)v1, (void*)len, (void*)pos, tmp}) HIPC(hipFree(p));
   } else if (n_set_edges) {
     hipLaunchKernelGGL(k_build_adjx, dim3(2048), dim3(256), 0, stream, ds.adj, ds.adj_off, sig, n_set_edges, adjx);
     HIPC(hipGetLastError());
@@ -596,7 +571,7 @@ int Snapshot::build_hash_tables() {
     HIPC(hipGetLastError());
   }
   HIPC(hipStreamSynchronize(stream));
-  HIPC(hipFree(sig));
+  sig.reset();
   ds.dset = dset;
   ds.dset_nb = buckets;
   ds.nmap = nm;
@@ -630,39 +605,37 @@ int Snapshot::build_reverse() {
   uint64_t* roff = nullptr;
   uint32_t* radj = nullptr;
   if (alloc((void**)&roff, ((size_t)nn + 1) * 8) || alloc((void**)&radj, (E + 1) * 4)) return -1;
-  unsigned long long* deg = nullptr;
-  HIPC(hipMalloc(&deg, ((size_t)nn + 1) * 8));
+  DevBuf<unsigned long long> deg;
+  HIPC(deg.reserve((size_t)nn + 1));
   HIPC(hipMemsetAsync(deg, 0, ((size_t)nn + 1) * 8, stream));
-  const uint32_t grid = (nn + 255) / 256;
   if (E) hipLaunchKernelGGL(k_indeg, dim3(4096), dim3(256), 0, stream, ds.adj, E, deg);
   HIPC(hipGetLastError());
   size_t tmp_bytes = 0;
-  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint64_t*)deg, roff, (size_t)nn + 1, stream));
-  void* tmp = nullptr;
-  HIPC(hipMalloc(&tmp, tmp_bytes + 16));
-  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, (uint64_t*)deg, roff, (size_t)nn + 1, stream));
+  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, (uint64_t*)deg.get(), roff, (size_t)nn + 1, stream));
+  DevBuf<void> tmp;
+  HIPC(tmp.reserve(tmp_bytes + 16));
+  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, (uint64_t*)deg.get(), roff, (size_t)nn + 1, stream));
   HIPC(hipMemcpyAsync(deg, roff, ((size_t)nn + 1) * 8, hipMemcpyDeviceToDevice, stream));
   if (E) {
-    uint32_t* src = nullptr;
-    HIPC(hipMalloc(&src, E * 4));
+    DevBuf<uint32_t> src;
+    HIPC(src.reserve(E));
     hipLaunchKernelGGL(k_row_nodes, dim3((uint32_t)std::min<uint64_t>(65536, (E + 64 * 256 - 1) / (64 * 256))), dim3(256),
                        0, stream, ds.adj_off, nn, E, src);
     hipLaunchKernelGGL(k_fill_radj, dim3((uint32_t)std::min<uint64_t>(65536, (E + 255) / 256)), dim3(256), 0, stream,
-                       ds.adj, (const uint32_t*)src, E, deg, radj);
+                       ds.adj, (const uint32_t*)src.get(), E, deg, radj);
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(stream));
-    HIPC(hipFree(src));
   }
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(stream));
-  HIPC(hipFree(tmp));
-  HIPC(hipFree(deg));
+  tmp.reset();
+  deg.reset();
   // holders: sort (subject, node) by subject
-  uint32_t *k0, *k1, *v0, *v1;
-  HIPC(hipMalloc(&k0, R * 4 + 4));
-  HIPC(hipMalloc(&k1, R * 4 + 4));
-  HIPC(hipMalloc(&v0, R * 4 + 4));
-  HIPC(hipMalloc(&v1, R * 4 + 4));
+  DevBuf<uint32_t> k0, k1, v0, v1;
+  HIPC(k0.reserve(R + 1));
+  HIPC(k1.reserve(R + 1));
+  HIPC(v0.reserve(R + 1));
+  HIPC(v1.reserve(R + 1));
   HIPC(hipMemcpyAsync(k0, csub, R * 4, hipMemcpyDeviceToDevice, stream));
   if (R)
     hipLaunchKernelGGL(k_row_nodes, dim3((uint32_t)std::min<uint64_t>(65536, (R + 64 * 256 - 1) / (64 * 256))), dim3(256), 0, stream,
@@ -671,14 +644,14 @@ int Snapshot::build_reverse() {
   hipcub::DoubleBuffer<uint32_t> kb(k0, k1), vb(v0, v1);
   tmp_bytes = 0;
   HIPC(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, kb, vb, (size_t)R, 0, 32, stream));
-  HIPC(hipMalloc(&tmp, tmp_bytes + 16));
+  HIPC(tmp.reserve(tmp_bytes + 16));
   HIPC(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, kb, vb, (size_t)R, 0, 32, stream));
-  unsigned long long* cnt;
-  HIPC(hipMalloc(&cnt, 16));
+  DevBuf<unsigned long long> cnt;
+  HIPC(cnt.reserve(2));
   HIPC(hipMemsetAsync(cnt, 0, 16, stream));
   if (R) {
     hipLaunchKernelGGL(k_count_runs, dim3(4096), dim3(256), 0, stream, kb.Current(), R, cnt);
-    hipLaunchKernelGGL(k_hold_maxid, dim3(4096), dim3(256), 0, stream, kb.Current(), R, (uint32_t*)(cnt + 1));
+    hipLaunchKernelGGL(k_hold_maxid, dim3(4096), dim3(256), 0, stream, kb.Current(), R, (uint32_t*)(cnt.get() + 1));
   }
   unsigned long long hcnt[2] = {0, 0};
   HIPC(hipMemcpyAsync(hcnt, cnt, 16, hipMemcpyDeviceToHost, stream));
@@ -705,7 +678,6 @@ int Snapshot::build_reverse() {
     HIPC(hipMemcpyAsync(hold, vb.Current(), R * 4, hipMemcpyDeviceToDevice, stream));
   }
   HIPC(hipStreamSynchronize(stream));
-  for (void* p : {(void*)k0, (void*)k1, (void*)v0, (void*)v1, tmp, (void*)cnt}) HIPC(hipFree(p));
   ds.radj_off = roff;
   ds.radj = radj;
   ds.hold = hold;
@@ -948,28 +920,27 @@ int Snapshot::create_synthetic(const kg_synth_params* p, const kg_rewrite_prog* 
   ds.wildcard_rel = 0;
   const uint32_t nn = L.n_nodes;
   ds.n_nodes = nn;
-  uint64_t *deg, *setdeg, *d_ro, *d_ao;
+  uint64_t *d_ro, *d_ao;
   if (alloc((void**)&d_ro, ((size_t)nn + 1) * 8) || alloc((void**)&d_ao, ((size_t)nn + 1) * 8)) return -1;
-  HIPC(hipMalloc(&deg, ((size_t)nn + 1) * 8));
-  HIPC(hipMalloc(&setdeg, ((size_t)nn + 1) * 8));
+  DevBuf<uint64_t> deg, setdeg;
+  HIPC(deg.reserve((size_t)nn + 1));
+  HIPC(setdeg.reserve((size_t)nn + 1));
   const uint32_t grid = (nn + 255) / 256;
   hipLaunchKernelGGL(k_synth_degrees, dim3(grid), dim3(256), 0, stream, L, nn, shard_rank, shard_n, deg, setdeg);
   HIPC(hipGetLastError());
   HIPC(hipMemsetAsync(deg + nn, 0, 8, stream));
   HIPC(hipMemsetAsync(setdeg + nn, 0, 8, stream));
   size_t tmp_bytes = 0;
-  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, deg, d_ro, nn + 1, stream));
-  void* tmp;
-  HIPC(hipMalloc(&tmp, tmp_bytes + 16));
-  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, deg, d_ro, nn + 1, stream));
-  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, setdeg, d_ao, nn + 1, stream));
+  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, deg.get(), d_ro, nn + 1, stream));
+  DevBuf<void> tmp;
+  HIPC(tmp.reserve(tmp_bytes + 16));
+  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, deg.get(), d_ro, nn + 1, stream));
+  HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, setdeg.get(), d_ao, nn + 1, stream));
   uint64_t tot[2];
   HIPC(hipMemcpyAsync(&tot[0], d_ro + nn, 8, hipMemcpyDeviceToHost, stream));
   HIPC(hipMemcpyAsync(&tot[1], d_ao + nn, 8, hipMemcpyDeviceToHost, stream));
   HIPC(hipStreamSynchronize(stream));
-  HIPC(hipFree(tmp));
-  HIPC(hipFree(deg));
-  HIPC(hipFree(setdeg));
+  tmp.reset(), deg.reset(), setdeg.reset();
   uint32_t *d_rs, *d_adj, *d_ns, *d_obj, *d_rel;
   if (alloc((void**)&d_rs, tot[0] * 4) || alloc((void**)&d_adj, tot[1] * 4) || alloc((void**)&d_ns, (size_t)nn * 4) ||
       alloc((void**)&d_obj, (size_t)nn * 4) || alloc((void**)&d_rel, (size_t)nn * 4))
@@ -1000,10 +971,10 @@ int Snapshot::create_synthetic(const kg_synth_params* p, const kg_rewrite_prog* 
 int Snapshot::device_flags() {
   const uint32_t nn = ds.n_nodes;
   uint8_t* f;
-  uint32_t* changed;
+  DevBuf<uint32_t> changed;
   if (alloc((void**)&f, (size_t)nn + 1)) return -1;
   ds.nflags = nullptr;
-  HIPC(hipMalloc(&changed, 4));
+  HIPC(changed.reserve(1));
   const uint32_t grid = (nn + 255) / 256;
   if (nn) {
     hipLaunchKernelGGL(k_flags_init, dim3(grid), dim3(256), 0, stream, ds, f);
@@ -1016,7 +987,6 @@ int Snapshot::device_flags() {
       if (!h) break;
     }
   }
-  HIPC(hipFree(changed));
   ds.nflags = f;
   return 0;
 }

@@ -848,3 +848,122 @@ def test_grid_dense_vs_oracle(ms, grid_cap, seed, tg_cap):
         allowed.append(out.mean())
     assert grid > 1000
     assert 0.01 < min(allowed) and 0.2 < max(allowed) < 0.99, allowed
+
+
+# ---- buffer regrowth (kg_buf.h): lanes, workspace scratch and their staging grow twice, then serve a small
+# batch again.  Lane::reserve and the workspace scratch start at 65 536 queries and grow to max(n, 2 x cap):
+# 70 000 forces the first regrow (to 131 072), 150 000 the second.
+REGROW_SIZES = (1_000, 70_000, 150_000, 1_000)
+REGROW_GMAX = 10
+_regrow_ref = {}
+
+
+def _regrow_snapshot():
+    return Snapshot.synthetic(200_000, seed=20250131)
+
+
+def _regrow_queries(torch, snap):
+    """(device queries [150 000, 7], the same on the host, the oracle's answers) -- the batches are prefixes of
+    one kg_synth_queries draw; the oracle runs once for the module."""
+    from keto_amd import _lib
+    n = max(REGROW_SIZES)
+    dq = torch.empty((n, 7), dtype=torch.int32, device="cuda")
+    _lib.check(_lib.load().kg_synth_queries(snap.handle, 29, n, dq.data_ptr()), "kg_synth_queries")
+    q = dq.cpu().numpy().view(np.uint32)
+    if "exp" not in _regrow_ref:
+        exp, oerr, _ = Oracle(snap.export(), 0).check_batch(q[:, :6], q[:, 6].view(np.int32), REGROW_GMAX,
+                                                            POLICY_CANONICAL, nthreads=8)
+        assert (oerr == 0).all()
+        _regrow_ref["q"], _regrow_ref["exp"] = q.copy(), exp
+    assert (q == _regrow_ref["q"]).all()  # the same snapshot gives the same queries
+    return dq, q, _regrow_ref["exp"]
+
+
+def _regrow_batch(torch, e, boundary, dq, q, n, o, er):
+    """One batch of the first n queries through a boundary; (answers, error codes) as numpy arrays."""
+    from keto_amd import _lib
+    if boundary == "host":
+        return e.batch_check_ids(q[:n])
+    if boundary == "packed":
+        out, pairs, n_err = e.batch_check_packed(q[:n])
+        err = np.zeros(n, np.uint32)
+        err[pairs[:, 0]] = pairs[:, 1]
+        assert n_err == len(pairs)
+        return out, err
+    _lib.check(_lib.load().kg_check_batch_device(e.snapshot.handle, dq.data_ptr(), n, e.config.max_read_depth,
+                                                 o.data_ptr(), er.data_ptr(), None, None), "kg_check_batch_device")
+    torch.cuda.synchronize()
+    return o[:n].cpu().numpy(), er[:n].cpu().numpy().view(np.uint32)
+
+
+@pytest.mark.parametrize("boundary", ["host", "packed", "device"])
+def test_check_buffers_regrow_vs_oracle(boundary):
+    """Batches of 1 000, 70 000, 150 000 and 1 000 queries on one engine, through host buffers (kg_check_batch),
+    the packed host boundary (kg_check_batch_packed) and device buffers (kg_check_batch_device): every batch
+    equals the oracle, and the small batch after the two regrows equals the first."""
+    torch = _torch()
+    snap = _regrow_snapshot()
+    dq, q, exp = _regrow_queries(torch, snap)
+    o = torch.empty(len(q), dtype=torch.uint8, device="cuda")
+    er = torch.empty(len(q), dtype=torch.int32, device="cuda")
+    e = Engine(snap, Config(REGROW_GMAX))
+    outs = []
+    for n in REGROW_SIZES:
+        out, err = _regrow_batch(torch, e, boundary, dq, q, n, o, er)
+        assert out.shape == (n,) and (err == 0).all(), n
+        assert (out == exp[:n]).all(), (n, np.nonzero(out != exp[:n])[0][:10])
+        outs.append(out)
+    assert (outs[0] == outs[-1]).all()
+    assert 0.05 < outs[2].mean() < 0.95
+    snap.close()
+
+
+def test_check_memory_flat_and_released():
+    """After the regrow sequence through all three boundaries, 10 more 150 000-query batches take no more
+    device memory (< 64 MiB, the bound of test_expand_lane_memory_stays_flat), and destroying the snapshot
+    gives back what it and its lanes, workspaces and staging held: free memory returns to within the same
+    bound of its value before the snapshot was created.  The tensors of this test stay allocated across
+    both readings; a first small snapshot has the runtime load its code objects and create its streams
+    before the first reading."""
+    torch = _torch()
+    bound = 64 << 20
+    n = max(REGROW_SIZES)
+    o = torch.empty(n, dtype=torch.uint8, device="cuda")
+    er = torch.empty(n, dtype=torch.int32, device="cuda")
+    from keto_amd import _lib
+    wq = torch.empty((n, 7), dtype=torch.int32, device="cuda")
+    warm = Snapshot.synthetic(20_000, seed=20250131)
+    _lib.check(_lib.load().kg_synth_queries(warm.handle, 29, 1000, wq.data_ptr()), "kg_synth_queries")
+    we = Engine(warm, Config(REGROW_GMAX))
+    for boundary in ("host", "packed", "device"):
+        _regrow_batch(torch, we, boundary, wq, wq[:1000].cpu().numpy().view(np.uint32), 1000, o, er)
+    warm.close()
+    del we, warm
+    torch.cuda.synchronize()
+    free_before = torch.cuda.mem_get_info(0)[0]
+    snap = _regrow_snapshot()
+    _lib.check(_lib.load().kg_synth_queries(snap.handle, 29, n, wq.data_ptr()), "kg_synth_queries")
+    dq, q = wq, wq.cpu().numpy().view(np.uint32)
+    e = Engine(snap, Config(REGROW_GMAX))
+    first = {}
+    for boundary in ("host", "packed", "device"):
+        for m in REGROW_SIZES:
+            out, err = _regrow_batch(torch, e, boundary, dq, q, m, o, er)
+            assert (err == 0).all()
+        first[boundary] = _regrow_batch(torch, e, boundary, dq, q, n, o, er)[0].copy()
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info(0)[0]
+    for i in range(10):
+        boundary = ("host", "packed", "device")[i % 3]
+        out, _ = _regrow_batch(torch, e, boundary, dq, q, n, o, er)
+        assert (out == first[boundary]).all()
+    torch.cuda.synchronize()
+    free1 = torch.cuda.mem_get_info(0)[0]
+    print(f"regrown: {free_before - free0} B taken, 10 more batches: {free0 - free1} B")
+    assert free0 - free1 < bound, (free0, free1)
+    snap.close()
+    del e, snap
+    torch.cuda.synchronize()
+    free_after = torch.cuda.mem_get_info(0)[0]
+    print(f"after the snapshot: {free_before - free_after} B below the first reading")
+    assert free_before - free_after < bound, (free_before, free_after)

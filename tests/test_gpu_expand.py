@@ -240,3 +240,30 @@ def test_expand_device_io_vs_oracle(gw, skip):
     _lib.device_to_host(off, buf.root_off, 8)
     assert buf.n_nodes == 0 and off[0] == 0
     L.kg_tree_free(buf)
+
+
+def test_expand_buffers_regrow_vs_oracle():
+    """One engine's expand buffers (the lane's for host output, the stream workspace's for device output)
+    sized for 200 roots, regrown for 2 000, then used for 200 again: host and device trees are equal on
+    every call, and the first 100 roots of each equal the oracle's BuildTree."""
+    from keto_amd.engine import Snapshot
+    from keto_amd.synth import hot_group_roots
+    snap = Snapshot.synthetic(300_000, seed=20250131)
+    ids = snap.synth_ids()
+    ex = ExpandEngine(snap)
+    ex.config.max_read_depth = 5
+    oracle = Oracle(snap.export(), 0)
+    want = {}  # the oracle's tree per root, computed once
+    for n in (200, 2000, 200):
+        roots = hot_group_roots(ids, n)
+        assert len(roots) == n
+        host = ex.build_trees_ids(roots)
+        dev = ex.build_trees_ids(roots, device=True)
+        for r, h, d in zip(roots, host, dev):
+            assert (h is None) == (d is None) and (h is None or (h.shape == d.shape and (h == d).all())), (n, r.tolist())
+        for r, d in zip(roots[:100], dev[:100]):
+            key = tuple(int(x) for x in r[:3])
+            if key not in want:
+                want[key] = oracle.expand(key[0], key[1], key[2], 0, 5)
+            _cmp_records(want[key], d, (n, r.tolist()))
+    snap.close()

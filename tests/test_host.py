@@ -185,6 +185,24 @@ def test_pack_queries_matches_header(tmp_path):
         _lib.pack_queries(bad)
 
 
+def test_buf_under_sanitizers(tmp_path):
+    """keto_amd/csrc/kg_buf.h (the owner of every device and pinned buffer, and the tree-output pool) over a
+    counting malloc, under AddressSanitizer and UBSan: tests/buf_check.cpp as a stand-alone child process
+    (reserve within capacity, free-before-allocate growth, failed allocations, moves, reset / release, the
+    pool's classes, keys and keep cap).  Host code only; machines with a GPU leave sanitizer runs out."""
+    import subprocess
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("sanitizer runs stay off GPU machines")
+    exe = tmp_path / "buf_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(ROOT, "keto_amd", "csrc"),
+                    os.path.join(ROOT, "tests", "buf_check.cpp"), "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "buf_check ok" in r.stdout
+
+
 def test_bench_device_packer_matches_pack_queries():
     """bench.py packs the headline's device-resident queries with torch ops (pack_queries_device); they
     must be the header's kg_pack_query rows bit for bit, as keto_amd._lib.pack_queries is (pinned above):
