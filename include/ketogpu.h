@@ -608,6 +608,41 @@ int kg_expand_batch_device(kg_snapshot* s, const kg_set* d_roots, size_t n, int3
                            void* stream);
 void kg_tree_free(kg_tree_buf* t);
 
+/* ---- reverse lookup ---------------------------------------------------------------------- */
+/* "Which objects of namespace ns may the subject do rel on?" (OpenFGA ListObjects, SpiceDB
+ * LookupResources; Keto has no such call: a caller enumerates the objects and checks each).  The answer
+ * of a request is defined through the check: the ascending object ids o, among the objects of ns that
+ * occur in the snapshot (as the object of a tuple or in a subject set), for which a check of
+ * ns:o#rel@subject with max_depth and the call's global_max_depth answers KG_IS_MEMBER.  An object
+ * whose check answers KG_ERROR is not listed: n_errors[i] counts such objects of request i and
+ * err_code[i] is the code of the lowest such object id (0: none) -- an undeclared relation lists
+ * nothing and reports every object of the namespace with KG_ERR_RELATION_NOT_FOUND.
+ * Relations without a rewrite and materialised unions are answered by one reverse walk from the rows
+ * that hold the subject (64 requests share a walk); every other relation by a check of every object.
+ * Host buffer in; the output arrays are library-allocated pinned memory, returned by the free call below.
+ * Request i owns objs[req_off[i] .. req_off[i+1]).  Thread-safe (a lane set per call, one replica,
+ * rotated).  Hash-sharded snapshots: -3.  kg_snapshot_tune key "lookup_cap" (tests): initial entries
+ * of the output list (0 = 64 Ki; a small value forces the regrow path). */
+typedef struct {
+  uint32_t ns, rel;         /* the objects' namespace and the relation asked for      */
+  uint32_t sns, sobj, srel; /* subject set, or sns = KG_SUBJECT_ID and the id in sobj */
+  int32_t max_depth;        /* <= 0: the global depth                                 */
+} kg_lookup;
+typedef struct {
+  uint64_t* req_off;   /* n_reqs + 1 */
+  uint32_t* objs;      /* ascending object ids per request */
+  uint32_t* err_code;  /* per request */
+  uint64_t* n_errors;  /* per request */
+  uint64_t n_reqs, n_objs;
+  /* per call: members listed by the walk / checks run to confirm candidates / of them members /
+   * reverse edges read / walk levels launched */
+  uint64_t exact, candidates, confirmed, reverse_edges, levels;
+  double kernel_ms;    /* device time of the call (HIP events) */
+  uint64_t pinned;     /* library use */
+} kg_lookup_buf;
+int kg_lookup_objects(kg_snapshot* s, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out);
+void kg_lookup_free(kg_lookup_buf* out);
+
 /* ---- errors ----------------------------------------------------------------------------- */
 /* Thread-local text of the last failing call; returns its length. */
 size_t kg_last_error(char* buf, size_t len);

@@ -99,6 +99,14 @@ class kg_tree_buf(C.Structure):
                 ("n_roots", C.c_uint64), ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
 
 
+class kg_lookup_buf(C.Structure):
+    _fields_ = [("req_off", C.POINTER(C.c_uint64)), ("objs", C.POINTER(C.c_uint32)),
+                ("err_code", C.POINTER(C.c_uint32)), ("n_errors", C.POINTER(C.c_uint64)),
+                ("n_reqs", C.c_uint64), ("n_objs", C.c_uint64), ("exact", C.c_uint64), ("candidates", C.c_uint64),
+                ("confirmed", C.c_uint64), ("reverse_edges", C.c_uint64), ("levels", C.c_uint64),
+                ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
+
+
 class kg_synth_params(C.Structure):
     _fields_ = [("n_tuples_target", C.c_uint64), ("seed", C.c_uint64), ("n_layers", C.c_uint32),
                 ("max_degree", C.c_uint32), ("set_fraction", C.c_float), ("doc_set_fraction", C.c_float),
@@ -115,7 +123,8 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_done", "kg_shard_levels", "kg_shard_back_list", "kg_shard_back_seed", "kg_shard_back_level", "kg_shard_refwd_seed",
            "kg_shard_held_words", "kg_shard_held", "kg_shard_result_slots", "kg_shard_bad_nodes", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats", "kg_batcher_reset_stats", "kg_batcher_destroy",
            "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
-           "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree"]
+           "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
+           "kg_lookup_objects", "kg_lookup_free"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -189,6 +198,10 @@ def load(path: str = LIB_PATH):
     L.kg_synth_queries.argtypes = [vp, u64, sz, vp]
     L.kg_expand_batch.argtypes = [vp, vp, sz, i32, C.POINTER(kg_tree_buf)]
     L.kg_expand_batch_device.argtypes = [vp, vp, sz, i32, C.POINTER(kg_tree_buf), vp]
+    L.kg_lookup_objects.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
+    L.kg_lookup_objects.restype = C.c_int
+    L.kg_lookup_free.argtypes = [C.POINTER(kg_lookup_buf)]
+    L.kg_lookup_free.restype = None
     L.kg_tree_free.argtypes = [C.POINTER(kg_tree_buf)]
     L.kg_tree_free.restype = None
     L.kg_last_error.argtypes = [C.c_char_p, sz]

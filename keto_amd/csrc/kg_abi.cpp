@@ -552,6 +552,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     s->lane_cv.notify_all();
     return 0;
   }
+  if (strcmp(key, "lookup_cap") == 0) {
+    if (value < 0 || value > (1ll << 32)) return set_error(-2, "lookup_cap must be in [0, 2^32]");
+    s->lookup_cap = (uint64_t)value;
+    return 0;
+  }
   if (strcmp(key, "back_edges") == 0) {
     if (value < 0 || value > (1 << 20)) return set_error(-2, "back_edges must be in [0, 2^20]");
     s->back_edges = (uint32_t)value;
@@ -983,6 +988,34 @@ int kg_expand_batch_device(kg_snapshot* sp, const kg_set* d_roots, size_t n, int
   std::lock_guard<std::mutex> lk(w->mu);
   return kg::expand_batch(s, w->stream, &w->exp, d_roots, n, global_max_depth, out, true);
   KG_GUARD_END
+}
+
+// One lane of one replica (rotated over the replicas): the walk's masks are per device, and a lookup is
+// one small batch of requests, not a stream of them.
+int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out) {
+  KG_GUARD_BEGIN
+  if (!sp || !out) return set_error(-2, "NULL argument");
+  if (n && !reqs) return set_error(-2, "reqs is NULL");
+  memset(out, 0, sizeof *out);
+  Snapshot* s = reinterpret_cast<Snapshot*>(sp);
+  if (s->shard_n > 1 || kg::shard_comm_of(s, nullptr))
+    return set_error(-3, "kg_lookup_objects: not supported on hash-sharded snapshots");
+  if (n == 0) {
+    out->req_off = (uint64_t*)calloc(1, 8);
+    if (!out->req_off) return set_error(-4, "host allocation failed");
+    return 0;
+  }
+  std::vector<kg::Lane*>* lanes = s->lanes_acquire();
+  if (!lanes) return -1;
+  LaneLease lease{s, lanes};
+  kg::Lane* L = (*lanes)[lanes->size() > 1 ? (size_t)(s->rr_next.fetch_add(1, std::memory_order_relaxed) % lanes->size()) : 0];
+  std::lock_guard<std::mutex> lk(L->w->mu);
+  return kg::lookup_objects(L->rep, L, reqs, n, global_max_depth, out);
+  KG_GUARD_END
+}
+
+void kg_lookup_free(kg_lookup_buf* out) {
+  if (out) kg::lookup_free(out);
 }
 
 void kg_tree_free(kg_tree_buf* t) {

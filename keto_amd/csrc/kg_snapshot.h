@@ -246,6 +246,7 @@ struct Lane {
   DevBuf<uint32_t> d_err;
   size_t cap = 0;  // queries the six above hold
   void* exp = nullptr;  // expand buffers of this lane (kg_expand.hip)
+  void* lk = nullptr;   // lookup buffers of this lane (kg_lookup.hip)
   // kg_check_batch_packed: packed queries on the device (staged through h_q) and the error list
   DevBuf<kg_query_packed> d_pk;
   DevBuf<uint32_t> d_el;  // count word, pad, then (index, code) pairs: room for every query of the chunk
@@ -350,6 +351,7 @@ struct Snapshot {
   size_t grid_ms_bytes = 1ull << 30;  // kg_snapshot_tune("grid_ms_bytes"): MS-BFS mask budget per workspace
   int grid_ms_words = 8;     // kg_snapshot_tune("grid_ms_words"): 64-bit words per MS-BFS mask (64 queries each)
   uint32_t grid_ms_tg_cap = 256;  // kg_snapshot_tune("grid_ms_tg_cap"): holders above which MS-BFS probes dset instead
+  uint64_t lookup_cap = 0;  // kg_snapshot_tune("lookup_cap"): initial output entries of a lookup (0 = 64 Ki; tests)
   uint64_t grid_ms_cap = 0;  // kg_snapshot_tune("grid_ms_cap"): MS-BFS entries per level buffer (0 = 16 Mi; tests)
   // replicas: the same snapshot on more devices (kg_snapshot_create's device mask); this object is
   // replica 0 and owns the others.  Host-buffer batches and expands are split over all of them.
@@ -468,6 +470,10 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
 void expand_bufs_free(void* bufs);
 void* tree_pool_get(size_t bytes);  // pinned host memory for tree outputs (kg_tree_free returns it)
 void tree_pool_put(void* p, size_t bytes);
+// kg_lookup.hip: kg_lookup_objects on lane L (the caller holds L->w->mu); lookup_free returns its output
+int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out);
+void lookup_free(kg_lookup_buf* out);
+void lookup_bufs_free(void* bufs);
 constexpr uint64_t KG_TREE_DEVICE = 0x100;  // kg_tree_buf.pinned: device-resident trees (low byte: the device)
 void* tree_dev_get(int device, size_t bytes);  // device memory for device-resident tree outputs
 void tree_dev_put(int device, void* p, size_t bytes);

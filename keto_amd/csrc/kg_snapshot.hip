@@ -339,6 +339,7 @@ void* Workspace::host_buf(size_t bytes) {
 Lane::~Lane() {
   if (device >= 0) (void)hipSetDevice(device);
   if (exp) expand_bufs_free(exp);
+  if (lk) lookup_bufs_free(lk);
   // the stream's workspace belongs to the replica (freed with it); the stream itself is ours -- synchronised
   // here, where the frees used to do it, because the buffers are released after this body
   if (stream) {

@@ -191,7 +191,7 @@ class Snapshot:
         """Engine knobs (kg_snapshot_tune; keto_amd/csrc/kg_abi.cpp tune_one lists them with their ranges;
         29 since round 6 removed the ones that measured flat): tier chain -- back_wgs, back_edges, stream_ecap,
         stream_wgs, stream_steal, grid_wgs, grid_cap, grid_reserve, grid_ms, grid_ms_words, grid_ms_bytes,
-        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; expand -- expand_gw, expand_gw_wait_us,
+        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap (tests); expand -- expand_gw, expand_gw_wait_us,
         expand_skip_lds (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
         shard_max_bytes, shard_force_overflow (tests), shard_bucket, shard_vis, shard_heavy, shard_budget,
         shard_back_budget, shard_remote_meta (read at the first binding).  Build-time, from the environment:
@@ -363,6 +363,45 @@ class Engine:
         if errs[0] is not None:
             raise errs[0]
         return allowed[0]
+
+    # ---- reverse lookup (no reference counterpart: OpenFGA ListObjects / SpiceDB LookupResources)
+    def lookup_objects_ids(self, reqs: np.ndarray,
+                           with_stats: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """reqs: (n,6) uint32 kg_lookup rows (ns, rel, sns, sobj, srel, max_depth).  Returns (req_off u64
+        [n+1], objs u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's objects are
+        objs[req_off[i]:req_off[i+1]] -- the objects of its namespace whose check is IsMember."""
+        reqs = np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6)
+        n = reqs.shape[0]
+        buf = _lib.kg_lookup_buf()
+        L = _lib.load()
+        _lib.check(L.kg_lookup_objects(self.snapshot.handle, _ptr(reqs) if n else None, n, self.config.max_read_depth,
+                                       C.byref(buf)), "kg_lookup_objects")
+        try:
+            m = int(buf.n_objs)
+            off = np.ctypeslib.as_array(buf.req_off, shape=(n + 1,)).copy()
+            objs = np.ctypeslib.as_array(buf.objs, shape=(m,)).copy() if m else np.zeros(0, np.uint32)
+            err = np.ctypeslib.as_array(buf.err_code, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+            nerr = np.ctypeslib.as_array(buf.n_errors, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            self.last_stats = {k: getattr(buf, k) for k in ("n_objs", "exact", "candidates", "confirmed",
+                                                            "reverse_edges", "levels", "kernel_ms")} if with_stats else None
+        finally:
+            L.kg_lookup_free(C.byref(buf))
+        return off, objs, err, nerr
+
+    def lookup_objects(self, namespace: str, relation: str, subject, rest_depth: int) -> List[str]:
+        """The objects of `namespace` on which `subject` (a SubjectSet or a subject-id string) has
+        `relation`, sorted by name.  Raises CheckError when the check of any object ends in an error."""
+        it = self.snapshot.interner
+        if isinstance(subject, SubjectSet):
+            sub = list(it.subject_set_ids(subject))
+        else:
+            sub = [SUBJECT_ID, it.obj_id(subject), 0]
+        row = np.asarray([it.ns_id(namespace), it.rel_id(relation), *sub, np.int32(rest_depth).view(np.uint32)],
+                         np.uint32)
+        _, objs, err, nerr = self.lookup_objects_ids(row)
+        if int(nerr[0]):
+            raise CheckError(int(err[0]))
+        return sorted(it.obj_name(int(o)) for o in objs)
 
 
 class ExpandEngine:

@@ -6,6 +6,7 @@ rule, status mirroring and the response shapes, as the reference's handlers do t
         GET/POST /relation-tuples/check/openapi    200 {"allowed": ...} always
                                                     internal/check/handler.go:101-232
         GET /relation-tuples/expand                 internal/expand/handler.go:81-107
+        GET /relation-tuples/list-objects           no reference counterpart (ListObjectsHandler)
   gRPC  CheckService.Check                          internal/check/handler.go:234-275
         ExpandService.Expand                        internal/expand/handler.go:109-146
 
@@ -106,8 +107,9 @@ def max_depth_from_query(q: dict) -> int:
         raise _bad(f"unable to parse 'max-depth' query parameter to int: {s!r}")
 
 
-def tuple_from_url_query(q: dict) -> RelationTuple:
-    """RelationTuple.FromURLQuery (ketoapi/enc_url_query.go:12-97)."""
+def subject_from_url_query(q: dict) -> Tuple[Optional[str], Optional[SubjectSet]]:
+    """The subject part of RelationTuple.FromURLQuery (ketoapi/enc_url_query.go:12-97): (subject id,
+    subject set), one of them set."""
     if "subject" in q:
         raise _bad(ERR_DROPPED_SUBJECT_KEY)
     has_id = SUBJECT_ID_KEY in q
@@ -126,6 +128,12 @@ def tuple_from_url_query(q: dict) -> RelationTuple:
         raise _bad(ERR_INCOMPLETE_SUBJECT)
     if sid is None and sset is None:
         raise _bad(ERR_NIL_SUBJECT)
+    return sid, sset
+
+
+def tuple_from_url_query(q: dict) -> RelationTuple:
+    """RelationTuple.FromURLQuery (ketoapi/enc_url_query.go:12-97)."""
+    sid, sset = subject_from_url_query(q)
     if "namespace" not in q or "object" not in q or "relation" not in q:
         raise _bad(ERR_INCOMPLETE_TUPLE)
     return RelationTuple(_get(q, "namespace"), _get(q, "object"), _get(q, "relation"), sid, sset)
@@ -245,3 +253,67 @@ class ExpandHandler:
         if tree is None:
             return {}
         return {"tree": tree.to_json()}
+
+
+class ListObjectsHandler:
+    """Reverse lookup over one engine (no reference counterpart; OpenFGA ListObjects' shape): the objects of
+    a namespace on which a subject has a relation, in name order, paged."""
+
+    DEFAULT_PAGE_SIZE = 100
+
+    def __init__(self, engine: Engine, mapper: Mapper):
+        self.engine, self.mapper = engine, mapper
+
+    def _list(self, namespace: str, relation: str, sid: Optional[str], sset: Optional[SubjectSet], max_depth: int,
+              page_size: int, page_token: str) -> dict:
+        if sid is None and sset is None:
+            raise _bad(ERR_NIL_SUBJECT)
+        try:  # the namespaces of the request as the check's mapper sees them
+            self.mapper.check_namespace(namespace)
+            if sset is not None:
+                self.mapper.check_namespace(sset.namespace)
+        except NamespaceNotFound as e:
+            raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        try:
+            at = int(page_token) if page_token else 0
+            if at < 0 or page_size < 1:
+                raise ValueError
+        except ValueError:
+            raise _bad("malformed page_token or page_size")
+        try:
+            names = self.engine.lookup_objects(namespace, relation, sset if sset is not None else sid, max_depth)
+        except CheckError as e:
+            raise HandlerError(500, str(e))
+        page = names[at:at + page_size]
+        return {"objects": page, "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
+
+    def get_list_objects(self, query: Union[str, Query]) -> Tuple[int, dict]:
+        """GET ?namespace=&relation=&subject_id= | subject_set.*=&max-depth=&page_size=&page_token=."""
+        try:
+            q = parse_query(query)
+            d = max_depth_from_query(q)
+            sid, sset = subject_from_url_query(q)
+            if "namespace" not in q or "relation" not in q:
+                raise _bad('incomplete request, provide "namespace", "relation", and a subject')
+            try:
+                size = parse_go_int(_get(q, "page_size")) if "page_size" in q else self.DEFAULT_PAGE_SIZE
+            except ValueError:
+                raise _bad("malformed page_token or page_size")
+            return 200, self._list(_get(q, "namespace"), _get(q, "relation"), sid, sset, d, size, _get(q, "page_token"))
+        except HandlerError as e:
+            return e.status, e.body()
+
+    def grpc_list_objects(self, req: dict) -> dict:
+        """req = {"namespace", "relation", "subject": {"id"} | {"set": {...}}, "max_depth", "page_size",
+        "page_token"}.  Raises HandlerError (grpc_code) on failure."""
+        sub = req.get("subject")
+        if not sub:
+            raise _bad(ERR_NIL_SUBJECT)
+        sid, sset = None, None
+        if "id" in sub:
+            sid = sub["id"]
+        else:
+            s = sub.get("set") or {}
+            sset = SubjectSet(s.get("namespace", ""), s.get("object", ""), s.get("relation", ""))
+        return self._list(req.get("namespace", ""), req.get("relation", ""), sid, sset, int(req.get("max_depth", 0)),
+                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))

@@ -134,6 +134,10 @@ class Mapper:
         if self.namespaces is not None and name not in self.namespaces:
             raise NamespaceNotFound(name)
 
+    def check_namespace(self, name: str) -> None:
+        """Raises NamespaceNotFound for a namespace the configuration does not have."""
+        self._check_ns(name)
+
     def from_tuple(self, t: RelationTuple) -> Tuple[int, int, int, int, int, int]:
         self._check_ns(t.namespace)
         if t.subject_set is not None:

@@ -1,0 +1,97 @@
+"""Reverse lookup against the brute force a caller needed before it: kg_lookup_objects for one request
+and for a batch of 64, and for the same requests every object of the namespace through
+kg_check_batch_device (queries resident in HBM, so the brute force pays no host transfer).
+
+  python tools/lookup_bench.py [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
+
+Prints one JSON line: median wall-clock milliseconds of both paths, their ratio, and the lookup call's
+reverse_edges / levels / n_objs.  The two answers are compared before anything is timed.
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+NS_DOC, REL_VIEWER, SUBJECT_ID = 0, 1, 0xFFFFFFFF  # the synthetic generator's ids (include/ketogpu.h)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tuples", type=int, default=2_000_000)
+    ap.add_argument("--depth", type=int, default=10)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    a = ap.parse_args(argv)
+    import torch
+    from keto_amd import _lib
+    from keto_amd.engine import Config, Engine, Snapshot
+    dev = torch.device("cuda", 0)
+    snap = Snapshot.synthetic(a.tuples)
+    eng = Engine(snap, Config(a.depth))
+    L = _lib.load()
+    rows = snap.export()
+    doc = rows[rows[:, 0] == NS_DOC]
+    sets = rows[(rows[:, 3] == NS_DOC)]
+    domain = np.unique(np.concatenate([doc[:, 1], sets[:, 4]]))  # the objects of namespace doc
+    # mid-degree users: the 64 users around the median of the number of rows that hold them
+    users, deg = np.unique(rows[rows[:, 3] == SUBJECT_ID, 4], return_counts=True)
+    order = np.argsort(deg, kind="stable")
+    mid = order[len(order) // 2 - 32:len(order) // 2 + 32]
+    subj = users[mid]
+    reqs64 = np.zeros((64, 6), np.uint32)
+    reqs64[:, 0], reqs64[:, 1], reqs64[:, 2], reqs64[:, 3] = NS_DOC, REL_VIEWER, SUBJECT_ID, subj
+    out = {"gpu": torch.cuda.get_device_name(0), "tuples": int(len(rows)), "nodes": snap.info()["nodes"],
+           "domain_objects": int(len(domain)), "depth": a.depth, "holder_rows_of_user": int(deg[mid[32]])}
+    stream = torch.cuda.current_stream(dev)
+    for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
+        n = len(reqs)
+        q = torch.zeros((n, len(domain), 7), dtype=torch.int32, device=dev)  # kg_query rows, built in HBM
+        q[:, :, 0], q[:, :, 2], q[:, :, 3] = NS_DOC, REL_VIEWER, -1  # -1: KG_SUBJECT_ID
+        q[:, :, 1] = torch.from_numpy(domain.view(np.int32)).to(dev)[None, :]
+        q[:, :, 4] = torch.from_numpy(reqs[:, 3].copy().view(np.int32)).to(dev)[:, None]
+        dq = q.reshape(-1, 7).contiguous()
+        d_out = torch.zeros(dq.shape[0], dtype=torch.uint8, device=dev)
+        d_err = torch.zeros(dq.shape[0], dtype=torch.int32, device=dev)
+
+        def brute():
+            _lib.check(L.kg_check_batch_device(snap.handle, dq.data_ptr(), dq.shape[0], a.depth, d_out.data_ptr(),
+                                               d_err.data_ptr(), None, C.c_void_p(stream.cuda_stream)), "check")
+            torch.cuda.synchronize()
+
+        def lookup():
+            return eng.lookup_objects_ids(reqs, with_stats=True)
+
+        brute()
+        off, objs, err, nerr = lookup()
+        member = (d_out.cpu().numpy() == 1).reshape(n, len(domain))
+        for i in range(n):  # the same answer both ways, before anything is timed
+            assert np.array_equal(objs[int(off[i]):int(off[i + 1])], domain[member[i]]), i
+        assert not nerr.any()
+        t = {}
+        for what, fn in (("lookup_ms", lookup), ("brute_ms", brute)):
+            xs = []
+            for k in range(a.warmup + a.reps):
+                t0 = time.perf_counter()
+                fn()
+                if k >= a.warmup:
+                    xs.append((time.perf_counter() - t0) * 1e3)
+            t[what] = statistics.median(xs)
+        lookup()
+        st = eng.last_stats
+        out[name] = {"requests": n, "checks_brute": int(dq.shape[0]), "lookup_ms": round(t["lookup_ms"], 4),
+                     "brute_ms": round(t["brute_ms"], 4), "brute_over_lookup": round(t["brute_ms"] / t["lookup_ms"], 2),
+                     "lookup_kernel_ms": round(st["kernel_ms"], 4), "reverse_edges": int(st["reverse_edges"]),
+                     "levels": int(st["levels"]), "n_objs": int(st["n_objs"]), "candidates": int(st["candidates"])}
+        del q, dq, d_out, d_err
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
