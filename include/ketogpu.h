@@ -643,6 +643,32 @@ typedef struct {
 int kg_lookup_objects(kg_snapshot* s, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out);
 void kg_lookup_free(kg_lookup_buf* out);
 
+/* "Which subject ids may do rel on ns:obj?" (OpenFGA ListUsers, SpiceDB LookupSubjects): the mirror of
+ * kg_lookup_objects.  The answer of a request is the ascending subject ids s, among the subject ids
+ * that occur in the snapshot as the SubjectID of a tuple, for which a check of ns:obj#rel@s with
+ * max_depth and the call's global_max_depth answers KG_IS_MEMBER.  Subject sets are never listed, and
+ * neither is an id that occurs in no tuple (even where a `not` rewrite would make its check a member).
+ * A subject id whose check answers KG_ERROR is not listed: n_errors[i] counts such ids of request i and
+ * err_code[i] is the code of the lowest one (0: none) -- an undeclared relation lists nothing and
+ * reports every subject id with KG_ERR_RELATION_NOT_FOUND.
+ * A pure root of a relation without a rewrite or of a materialised union is answered by one forward
+ * walk over the set adjacency (64 requests share a walk; no reverse index is needed); every other
+ * request by a check of every subject id.
+ * The output is a kg_lookup_buf, returned by kg_lookup_free.  For this call: objs holds the ascending
+ * subject ids per request (objs[req_off[i] .. req_off[i+1])); exact is the number of (request, id) keys
+ * the walk emitted before duplicates are dropped (an id is usually reached through several nodes);
+ * candidates and confirmed are the checks run and, of them, the members; reverse_edges is the number
+ * of set edges plus check-row entries the walk read; levels is the number of walk levels launched.
+ * Thread-safety, hash-sharded snapshots (-3) and the "lookup_cap" tune key as kg_lookup_objects;
+ * "lookup_domain_rows" (tests): 1 = list the domain from the check rows even where the holder bitmap
+ * exists. */
+typedef struct {
+  uint32_t ns, obj, rel; /* the object and the relation asked for */
+  int32_t max_depth;     /* <= 0: the global depth                */
+} kg_lookup_subj;
+int kg_lookup_subjects(kg_snapshot* s, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
+                       kg_lookup_buf* out);
+
 /* ---- errors ----------------------------------------------------------------------------- */
 /* Thread-local text of the last failing call; returns its length. */
 size_t kg_last_error(char* buf, size_t len);

@@ -13,7 +13,7 @@ def __getattr__(name):  # engine pieces load the HIP library lazily
     if name in ("Engine", "ExpandEngine", "Snapshot", "Registry", "Config", "CheckError", "Result", "queries_array"):
         from . import engine
         return getattr(engine, name)
-    if name in ("CheckHandler", "ExpandHandler", "ListObjectsHandler", "HandlerError"):
+    if name in ("CheckHandler", "ExpandHandler", "ListObjectsHandler", "ListSubjectsHandler", "HandlerError"):
         from . import handlers
         return getattr(handlers, name)
     raise AttributeError(name)

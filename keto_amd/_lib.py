@@ -124,7 +124,7 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_held_words", "kg_shard_held", "kg_shard_result_slots", "kg_shard_bad_nodes", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats", "kg_batcher_reset_stats", "kg_batcher_destroy",
            "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
            "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
-           "kg_lookup_objects", "kg_lookup_free"]
+           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -200,6 +200,8 @@ def load(path: str = LIB_PATH):
     L.kg_expand_batch_device.argtypes = [vp, vp, sz, i32, C.POINTER(kg_tree_buf), vp]
     L.kg_lookup_objects.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
     L.kg_lookup_objects.restype = C.c_int
+    L.kg_lookup_subjects.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
+    L.kg_lookup_subjects.restype = C.c_int
     L.kg_lookup_free.argtypes = [C.POINTER(kg_lookup_buf)]
     L.kg_lookup_free.restype = None
     L.kg_tree_free.argtypes = [C.POINTER(kg_tree_buf)]

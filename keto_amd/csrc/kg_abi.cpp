@@ -557,6 +557,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     s->lookup_cap = (uint64_t)value;
     return 0;
   }
+  if (strcmp(key, "lookup_domain_rows") == 0) {
+    if (value < 0 || value > 1) return set_error(-2, "lookup_domain_rows must be 0 or 1");
+    s->lookup_domain_rows = (int)value;
+    return 0;
+  }
   if (strcmp(key, "back_edges") == 0) {
     if (value < 0 || value > (1 << 20)) return set_error(-2, "back_edges must be in [0, 2^20]");
     s->back_edges = (uint32_t)value;
@@ -991,15 +996,15 @@ int kg_expand_batch_device(kg_snapshot* sp, const kg_set* d_roots, size_t n, int
 }
 
 // One lane of one replica (rotated over the replicas): the walk's masks are per device, and a lookup is
-// one small batch of requests, not a stream of them.
-int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out) {
-  KG_GUARD_BEGIN
+// one small batch of requests, not a stream of them.  run(replica, lane): the lookup itself.
+static int lookup_call(const char* name, kg_snapshot* sp, const void* reqs, size_t n, kg_lookup_buf* out,
+                       const std::function<int(Snapshot*, kg::Lane*)>& run) {
   if (!sp || !out) return set_error(-2, "NULL argument");
   if (n && !reqs) return set_error(-2, "reqs is NULL");
   memset(out, 0, sizeof *out);
   Snapshot* s = reinterpret_cast<Snapshot*>(sp);
   if (s->shard_n > 1 || kg::shard_comm_of(s, nullptr))
-    return set_error(-3, "kg_lookup_objects: not supported on hash-sharded snapshots");
+    return set_error(-3, "%s: not supported on hash-sharded snapshots", name);
   if (n == 0) {
     out->req_off = (uint64_t*)calloc(1, 8);
     if (!out->req_off) return set_error(-4, "host allocation failed");
@@ -1010,7 +1015,23 @@ int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t 
   LaneLease lease{s, lanes};
   kg::Lane* L = (*lanes)[lanes->size() > 1 ? (size_t)(s->rr_next.fetch_add(1, std::memory_order_relaxed) % lanes->size()) : 0];
   std::lock_guard<std::mutex> lk(L->w->mu);
-  return kg::lookup_objects(L->rep, L, reqs, n, global_max_depth, out);
+  return run(L->rep, L);
+}
+
+int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out) {
+  KG_GUARD_BEGIN
+  return lookup_call("kg_lookup_objects", sp, reqs, n, out, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_objects(rep, L, reqs, n, global_max_depth, out);
+  });
+  KG_GUARD_END
+}
+
+int kg_lookup_subjects(kg_snapshot* sp, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
+                       kg_lookup_buf* out) {
+  KG_GUARD_BEGIN
+  return lookup_call("kg_lookup_subjects", sp, reqs, n, out, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_subjects(rep, L, reqs, n, global_max_depth, out);
+  });
   KG_GUARD_END
 }
 

@@ -352,6 +352,9 @@ struct Snapshot {
   int grid_ms_words = 8;     // kg_snapshot_tune("grid_ms_words"): 64-bit words per MS-BFS mask (64 queries each)
   uint32_t grid_ms_tg_cap = 256;  // kg_snapshot_tune("grid_ms_tg_cap"): holders above which MS-BFS probes dset instead
   uint64_t lookup_cap = 0;  // kg_snapshot_tune("lookup_cap"): initial output entries of a lookup (0 = 64 Ki; tests)
+  // kg_snapshot_tune("lookup_domain_rows") (tests): 1 = kg_lookup_subjects lists its domain from the check
+  // rows even where the holder bitmap exists (what a snapshot without reverse indexes does)
+  int lookup_domain_rows = 0;
   uint64_t grid_ms_cap = 0;  // kg_snapshot_tune("grid_ms_cap"): MS-BFS entries per level buffer (0 = 16 Mi; tests)
   // replicas: the same snapshot on more devices (kg_snapshot_create's device mask); this object is
   // replica 0 and owns the others.  Host-buffer batches and expands are split over all of them.
@@ -470,8 +473,10 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
 void expand_bufs_free(void* bufs);
 void* tree_pool_get(size_t bytes);  // pinned host memory for tree outputs (kg_tree_free returns it)
 void tree_pool_put(void* p, size_t bytes);
-// kg_lookup.hip: kg_lookup_objects on lane L (the caller holds L->w->mu); lookup_free returns its output
+// kg_lookup.hip: kg_lookup_objects / kg_lookup_subjects on lane L (the caller holds L->w->mu); lookup_free returns its output
 int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out);
+int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
+                    kg_lookup_buf* out);
 void lookup_free(kg_lookup_buf* out);
 void lookup_bufs_free(void* bufs);
 constexpr uint64_t KG_TREE_DEVICE = 0x100;  // kg_tree_buf.pinned: device-resident trees (low byte: the device)

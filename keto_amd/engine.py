@@ -191,7 +191,7 @@ class Snapshot:
         """Engine knobs (kg_snapshot_tune; keto_amd/csrc/kg_abi.cpp tune_one lists them with their ranges;
         29 since round 6 removed the ones that measured flat): tier chain -- back_wgs, back_edges, stream_ecap,
         stream_wgs, stream_steal, grid_wgs, grid_cap, grid_reserve, grid_ms, grid_ms_words, grid_ms_bytes,
-        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap (tests); expand -- expand_gw, expand_gw_wait_us,
+        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests); expand -- expand_gw, expand_gw_wait_us,
         expand_skip_lds (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
         shard_max_bytes, shard_force_overflow (tests), shard_bucket, shard_vis, shard_heavy, shard_budget,
         shard_back_budget, shard_remote_meta (read at the first binding).  Build-time, from the environment:
@@ -370,12 +370,16 @@ class Engine:
         """reqs: (n,6) uint32 kg_lookup rows (ns, rel, sns, sobj, srel, max_depth).  Returns (req_off u64
         [n+1], objs u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's objects are
         objs[req_off[i]:req_off[i+1]] -- the objects of its namespace whose check is IsMember."""
-        reqs = np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6)
+        return self._lookup("kg_lookup_objects", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6), with_stats)
+
+    def _lookup(self, call: str, reqs: np.ndarray, with_stats: bool):
+        """One kg_lookup_objects / kg_lookup_subjects call: the four output arrays copied out of the
+        kg_lookup_buf, its counters in last_stats."""
         n = reqs.shape[0]
         buf = _lib.kg_lookup_buf()
         L = _lib.load()
-        _lib.check(L.kg_lookup_objects(self.snapshot.handle, _ptr(reqs) if n else None, n, self.config.max_read_depth,
-                                       C.byref(buf)), "kg_lookup_objects")
+        _lib.check(getattr(L, call)(self.snapshot.handle, _ptr(reqs) if n else None, n, self.config.max_read_depth,
+                                    C.byref(buf)), call)
         try:
             m = int(buf.n_objs)
             off = np.ctypeslib.as_array(buf.req_off, shape=(n + 1,)).copy()
@@ -402,6 +406,26 @@ class Engine:
         if int(nerr[0]):
             raise CheckError(int(err[0]))
         return sorted(it.obj_name(int(o)) for o in objs)
+
+    # ---- subject lookup (OpenFGA ListUsers / SpiceDB LookupSubjects)
+    def lookup_subjects_ids(self, reqs: np.ndarray,
+                            with_stats: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """reqs: (n,4) uint32 kg_lookup_subj rows (ns, obj, rel, max_depth).  Returns (req_off u64 [n+1],
+        subject ids u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's subject ids
+        are ids[req_off[i]:req_off[i+1]] -- the subject ids of the snapshot's tuples whose check on the
+        request's object is IsMember."""
+        return self._lookup("kg_lookup_subjects", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 4), with_stats)
+
+    def lookup_subjects(self, namespace: str, object: str, relation: str, rest_depth: int) -> List[str]:
+        """The subject ids that have `relation` on `namespace:object`, sorted by name.  Raises CheckError
+        when the check of any subject id ends in an error."""
+        it = self.snapshot.interner
+        row = np.asarray([it.ns_id(namespace), it.obj_id(object), it.rel_id(relation),
+                          np.int32(rest_depth).view(np.uint32)], np.uint32)
+        _, ids, err, nerr = self.lookup_subjects_ids(row)
+        if int(nerr[0]):
+            raise CheckError(int(err[0]))
+        return sorted(it.obj_name(int(i)) for i in ids)
 
 
 class ExpandEngine:

@@ -7,6 +7,7 @@ rule, status mirroring and the response shapes, as the reference's handlers do t
                                                     internal/check/handler.go:101-232
         GET /relation-tuples/expand                 internal/expand/handler.go:81-107
         GET /relation-tuples/list-objects           no reference counterpart (ListObjectsHandler)
+        GET /relation-tuples/list-subjects          no reference counterpart (ListSubjectsHandler)
   gRPC  CheckService.Check                          internal/check/handler.go:234-275
         ExpandService.Expand                        internal/expand/handler.go:109-146
 
@@ -316,4 +317,58 @@ class ListObjectsHandler:
             s = sub.get("set") or {}
             sset = SubjectSet(s.get("namespace", ""), s.get("object", ""), s.get("relation", ""))
         return self._list(req.get("namespace", ""), req.get("relation", ""), sid, sset, int(req.get("max_depth", 0)),
+                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))
+
+
+class ListSubjectsHandler:
+    """Subject lookup over one engine (no reference counterpart; OpenFGA ListUsers' shape): the subject ids
+    that have a relation on an object, in name order, paged like ListObjectsHandler."""
+
+    DEFAULT_PAGE_SIZE = ListObjectsHandler.DEFAULT_PAGE_SIZE
+
+    def __init__(self, engine: Engine, mapper: Mapper):
+        self.engine, self.mapper = engine, mapper
+
+    def _list(self, namespace: str, object: str, relation: str, max_depth: int, page_size: int,
+              page_token: str) -> dict:
+        try:
+            self.mapper.check_namespace(namespace)
+        except NamespaceNotFound as e:
+            raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        try:
+            at = int(page_token) if page_token else 0
+            if at < 0 or page_size < 1:
+                raise ValueError
+        except ValueError:
+            raise _bad("malformed page_token or page_size")
+        try:
+            names = self.engine.lookup_subjects(namespace, object, relation, max_depth)
+        except CheckError as e:
+            raise HandlerError(500, str(e))
+        page = names[at:at + page_size]
+        return {"subject_ids": page, "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
+
+    def get_list_subjects(self, query: Union[str, Query]) -> Tuple[int, dict]:
+        """GET ?namespace=&object=&relation=&max-depth=&page_size=&page_token=."""
+        try:
+            q = parse_query(query)
+            d = max_depth_from_query(q)
+            if "namespace" not in q or "object" not in q or "relation" not in q:
+                raise _bad('incomplete request, provide "namespace", "object" and "relation"')
+            try:
+                size = parse_go_int(_get(q, "page_size")) if "page_size" in q else self.DEFAULT_PAGE_SIZE
+            except ValueError:
+                raise _bad("malformed page_token or page_size")
+            return 200, self._list(_get(q, "namespace"), _get(q, "object"), _get(q, "relation"), d, size,
+                                   _get(q, "page_token"))
+        except HandlerError as e:
+            return e.status, e.body()
+
+    def grpc_list_subjects(self, req: dict) -> dict:
+        """req = {"namespace", "object", "relation", "max_depth", "page_size", "page_token"}.  Raises
+        HandlerError (grpc_code) on failure."""
+        for k in ("namespace", "object", "relation"):
+            if not req.get(k):
+                raise _bad('incomplete request, provide "namespace", "object" and "relation"')
+        return self._list(req["namespace"], req["object"], req["relation"], int(req.get("max_depth", 0)),
                           int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))

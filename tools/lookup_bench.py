@@ -2,7 +2,10 @@
 and for a batch of 64, and for the same requests every object of the namespace through
 kg_check_batch_device (queries resident in HBM, so the brute force pays no host transfer).
 
-  python tools/lookup_bench.py [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
+  python tools/lookup_bench.py [--mode objects|subjects] [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
+
+--mode subjects measures the mirror image the same way: kg_lookup_subjects for one doc and for 64 docs
+against every subject id of the snapshot's tuples through kg_check_batch_device.
 
 Prints one JSON line: median wall-clock milliseconds of both paths, their ratio, and the lookup call's
 reverse_edges / levels / n_objs.  The two answers are compared before anything is timed.
@@ -24,6 +27,7 @@ NS_DOC, REL_VIEWER, SUBJECT_ID = 0, 1, 0xFFFFFFFF  # the synthetic generator's i
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("objects", "subjects"), default="objects")
     ap.add_argument("--tuples", type=int, default=2_000_000)
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
@@ -49,13 +53,25 @@ def main(argv=None):
     reqs64[:, 0], reqs64[:, 1], reqs64[:, 2], reqs64[:, 3] = NS_DOC, REL_VIEWER, SUBJECT_ID, subj
     out = {"gpu": torch.cuda.get_device_name(0), "tuples": int(len(rows)), "nodes": snap.info()["nodes"],
            "domain_objects": int(len(domain)), "depth": a.depth, "holder_rows_of_user": int(deg[mid[32]])}
+    if a.mode == "subjects":
+        # mid-reach docs: the 64 doc#viewer nodes around the median check-row length; the domain is every subject id
+        viewer = doc[doc[:, 2] == REL_VIEWER]
+        docs, rlen = np.unique(viewer[:, 1], return_counts=True)
+        order = np.argsort(rlen, kind="stable")
+        mid = order[len(order) // 2 - 32:len(order) // 2 + 32]
+        domain = users
+        reqs64 = np.zeros((64, 4), np.uint32)
+        reqs64[:, 0], reqs64[:, 1], reqs64[:, 2] = NS_DOC, docs[mid], REL_VIEWER
+        out = {"gpu": out["gpu"], "tuples": out["tuples"], "nodes": out["nodes"], "domain_subject_ids": int(len(domain)),
+               "depth": a.depth, "check_row_of_doc": int(rlen[mid[32]])}
     stream = torch.cuda.current_stream(dev)
     for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
         n = len(reqs)
         q = torch.zeros((n, len(domain), 7), dtype=torch.int32, device=dev)  # kg_query rows, built in HBM
         q[:, :, 0], q[:, :, 2], q[:, :, 3] = NS_DOC, REL_VIEWER, -1  # -1: KG_SUBJECT_ID
-        q[:, :, 1] = torch.from_numpy(domain.view(np.int32)).to(dev)[None, :]
-        q[:, :, 4] = torch.from_numpy(reqs[:, 3].copy().view(np.int32)).to(dev)[:, None]
+        d_dom = torch.from_numpy(domain.view(np.int32)).to(dev)[None, :]
+        d_req = torch.from_numpy(reqs[:, 3 if a.mode == "objects" else 1].copy().view(np.int32)).to(dev)[:, None]
+        q[:, :, 1], q[:, :, 4] = (d_dom, d_req) if a.mode == "objects" else (d_req, d_dom)
         dq = q.reshape(-1, 7).contiguous()
         d_out = torch.zeros(dq.shape[0], dtype=torch.uint8, device=dev)
         d_err = torch.zeros(dq.shape[0], dtype=torch.int32, device=dev)
@@ -66,6 +82,8 @@ def main(argv=None):
             torch.cuda.synchronize()
 
         def lookup():
+            if a.mode == "subjects":
+                return eng.lookup_subjects_ids(reqs, with_stats=True)
             return eng.lookup_objects_ids(reqs, with_stats=True)
 
         brute()
@@ -88,7 +106,7 @@ def main(argv=None):
         out[name] = {"requests": n, "checks_brute": int(dq.shape[0]), "lookup_ms": round(t["lookup_ms"], 4),
                      "brute_ms": round(t["brute_ms"], 4), "brute_over_lookup": round(t["brute_ms"] / t["lookup_ms"], 2),
                      "lookup_kernel_ms": round(st["kernel_ms"], 4), "reverse_edges": int(st["reverse_edges"]),
-                     "levels": int(st["levels"]), "n_objs": int(st["n_objs"]), "candidates": int(st["candidates"])}
+                     "levels": int(st["levels"]), "n_objs": int(st["n_objs"]), "exact": int(st["exact"]), "candidates": int(st["candidates"])}
         del q, dq, d_out, d_err
     print(json.dumps(out))
 
