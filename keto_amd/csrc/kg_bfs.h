@@ -144,6 +144,17 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t v, int src) {
 
 __device__ __forceinline__ uint32_t lanes_below(uint64_t m) { return __popcll(m & ((1ull << lane_id()) - 1)); }
 
+// Reserves `count` consecutive entries for this lane behind a 64-bit counter: one atomic per wave (none
+// when no lane asks for an entry).  Returns the lane's first position.  Must be called with every lane
+// of the wave active.
+__device__ __forceinline__ uint64_t wave_reserve64(unsigned long long* counter, uint32_t count) {
+  uint32_t total;
+  const uint32_t excl = wave_excl_scan(count, &total);
+  unsigned long long base = 0;
+  if (total && lane_id() == 0) base = atomicAdd(counter, (unsigned long long)total);
+  return shfl64(base, 0) + excl;
+}
+
 // largest j in [0, n) with pref[j] <= e (pref non-decreasing, pref[0] = 0)
 __device__ __forceinline__ int owner_search(const uint32_t* pref, int n, uint32_t e) {
   int lo = 0, hi = n;

@@ -229,13 +229,12 @@ __global__ __launch_bounds__(256) void k_resolve(DevSnap s, const kg_query* __re
       uint32_t sn = nmap_find(s, x.t.sns, x.t.srel, x.t.sobj);
       subj = sn == NONE ? NONE : (SET_BIT | sn);
     }
-    int32_t d = x.max_depth;
-    if (d <= 0 || global < d) d = global;  // engine.go:68-70
+    const int32_t d = clamp_depth(x.max_depth, global);
     const uint8_t rf = relflag(s, x.t.ns, x.t.rel);
     if (node == NONE) {
       // a materialised union relation without a node for this object: none of its components has a
       // node either (the node exists as soon as one does), so every branch is NotMember
-      const bool virt = s.virt && x.t.ns < s.n_ns && x.t.rel < s.n_rel && s.virt[(size_t)x.t.ns * s.n_rel + x.t.rel];
+      const bool virt = rel_is_union(s, x.t.ns, x.t.rel);
       route = rf && !virt ? ROUTE_GENERAL : ROUTE_DONE;
     } else {
       // the node's flags ride in its node-map slot (a random nflags read per query otherwise)

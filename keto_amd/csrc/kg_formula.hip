@@ -94,8 +94,7 @@ __global__ __launch_bounds__(FS_BLOCK) void k_fsplit(DevSnap s, const int32_t* _
   if (!valid) return;
   uint2 r = make_uint2(NONE, NONE);
   if (take) {
-    int32_t d = x.max_depth;
-    if (d <= 0 || global < d) d = global;  // engine.go:68-70: the leaves run at the clamped depth
+    const int32_t d = clamp_depth(x.max_depth, global);  // the leaves run at the clamped depth
     const FPlan& P = plans[pi];
     const uint32_t base = n + wbase + off;
     for (uint32_t j = 0; j < P.n_leaves; j++) {

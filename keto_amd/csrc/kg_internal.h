@@ -242,6 +242,16 @@ __host__ __device__ __forceinline__ uint8_t relflag(const DevSnap& s, uint32_t n
   return s.relflags[(size_t)ns * s.n_rel + rel];
 }
 
+// Is (ns, rel) a materialised union relation (kg_augment.hip)?
+__host__ __device__ __forceinline__ bool rel_is_union(const DevSnap& s, uint32_t ns, uint32_t rel) {
+  return s.virt && ns < s.n_ns && rel < s.n_rel && s.virt[(size_t)ns * s.n_rel + rel];
+}
+
+// The rest depth a request runs at: its own max_depth, or the global one where that is unset or smaller.
+__host__ __device__ __forceinline__ int32_t clamp_depth(int32_t d, int32_t global) {
+  return d <= 0 || global < d ? global : d;  // engine.go:68-70
+}
+
 // Resolved query as stored in HBM by the mapping kernel.
 struct RQuery {
   uint32_t node;   // root node id or NONE

@@ -1,9 +1,11 @@
-// kg_lookup.hip -- reverse lookup: the objects of a namespace a subject has a relation on
-// (OpenFGA ListObjects / SpiceDB LookupResources; no reference counterpart in Keto).
+// kg_lookup.hip -- the two lookups, neither with a reference counterpart in Keto: the objects of a
+// namespace a subject has a relation on (kg_lookup_objects: OpenFGA ListObjects / SpiceDB LookupResources)
+// and the subject ids that hold a relation on one object (kg_lookup_subjects: ListUsers / LookupSubjects).
 //
-// The answer of a request (ns, rel, subject, max_depth) is defined through the check: the ascending
-// object ids o with a node (ns, o, *) for which CheckIsMember(ns:o#rel@subject, max_depth) is IsMember.
-// A request is answered in one of three modes (k_lk_resolve):
+// The answer is defined through the check: for a request (ns, rel, subject, max_depth) the ascending
+// object ids o with a node (ns, o, *) for which CheckIsMember(ns:o#rel@subject, max_depth) is IsMember; for
+// (ns, obj, rel, max_depth) the subject ids of tuples with that check on ns:obj#rel.  An object request is
+// answered in one of three modes (k_lk_resolve):
 //   reverse        (ns, rel) has no rewrite or is a materialised union, and the reverse indexes exist:
 //                  every member is a node of (ns, rel); a PURE node is a member iff its reverse distance
 //                  from a holder of the subject is <= D-1 (what k_back decides for one root), so one
@@ -11,15 +13,15 @@
 //   confirm-nodes  the same without reverse indexes: every node of (ns, rel) is confirmed.
 //   confirm-all    any other relation (interpreter / formula split / undeclared): every object of the
 //                  namespace is confirmed.
-// "Confirmed" = run through check_batch_device as kg_query rows built on the device; no check kernel
-// is touched.  The walk is level-synchronous and bit-parallel over groups of 64 requests: a dense u64
-// visited mask per node (bit = request), a frontier list per level, work assigned per reverse edge
-// through a prefix over the frontier rows' lengths.  The masks are cleared by replaying the list of
-// touched nodes, so a lookup costs what it reaches, not n_nodes.
+// A subject request (k_ls_resolve) with a pure root of such a relation is answered by a FORWARD walk over
+// adj, everything else by confirming every subject id.  "Confirmed" = run through check_batch_device as
+// kg_query rows built on the device; no check kernel is touched.
 //
-// Subject lookup (kg_lookup_subjects, the second half of this file) is the mirror image: the subject ids
-// that hold a relation on one object.  A pure root of such a relation is answered by a FORWARD walk over
-// adj with the same masks, lists and output tail; everything else by a check of every subject id.
+// There is one walk (walk_groups) with two direction policies (ReverseWalk, ForwardWalk).  It is level-
+// synchronous and bit-parallel over groups of 64 requests: a dense u64 visited mask per node (bit =
+// request), a frontier list per level, work assigned per edge through a prefix over the frontier rows'
+// lengths.  The masks are cleared by replaying the list of touched nodes, so a lookup costs what it
+// reaches, not n_nodes.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -27,6 +29,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <set>
+#include <type_traits>
 #include <vector>
 
 #include "kg_bfs.h"
@@ -96,8 +100,6 @@ struct CandTab {
   uint32_t M;
 };
 
-__device__ __forceinline__ u64 wave_bcast64(u64 v, int src) { return shfl64(v, src); }
-
 // Appends val where pred; one atomic per wave; entries past cap are dropped and flagged.
 __device__ __forceinline__ void lk_append32(bool pred, uint32_t val, uint32_t* list, uint32_t* count, uint32_t cap,
                                             uint32_t* over) {
@@ -113,35 +115,28 @@ __device__ __forceinline__ void lk_append32(bool pred, uint32_t val, uint32_t* l
     else *over = 1;
   }
 }
-__device__ __forceinline__ void lk_append64(bool pred, u64 val, u64* list, u64* count, u64 cap) {
-  const uint64_t m = __ballot(pred);
-  if (!m) return;
-  const int leader = __ffsll((unsigned long long)m) - 1;
-  u64 base = 0;
-  if (lane_id() == leader) base = atomicAdd(count, (u64)__popcll(m));
-  base = wave_bcast64(base, leader);
-  if (pred) {
-    const u64 pos = base + lanes_below(m);
-    if (pos < cap) list[pos] = val;
-  }
+// The same behind a 64-bit TRUE count (nothing flagged: the count says so).
+template <class V>
+__device__ __forceinline__ void lk_append64(bool pred, V val, V* list, u64* count, u64 cap) {
+  const u64 pos = wave_reserve64(count, pred ? 1u : 0u);
+  if (pred && pos < cap) list[pos] = val;
 }
 
-__device__ __forceinline__ uint32_t lk_find64(const u64* a, uint32_t n, u64 key) {
-  uint32_t lo = 0, hi = n;
+// The first index of the ascending a[0, n) whose entry is >= key (n: none).
+template <class T, class I>
+__device__ __forceinline__ I lk_lower_bound(const T* a, I n, T key) {
+  I lo = 0, hi = n;
   while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
+    const I mid = (lo + hi) >> 1;
     if (a[mid] < key) lo = mid + 1;
     else hi = mid;
   }
-  return lo < n && a[lo] == key ? lo : NONE;
+  return lo;
 }
-__device__ __forceinline__ uint32_t lk_find32(const uint32_t* a, uint32_t n, uint32_t key) {
-  uint32_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint32_t mid = (lo + hi) >> 1;
-    if (a[mid] < key) lo = mid + 1;
-    else hi = mid;
-  }
+// The index of key in the ascending a[0, n), or NONE.
+template <class T>
+__device__ __forceinline__ uint32_t lk_find(const T* a, uint32_t n, T key) {
+  const uint32_t lo = lk_lower_bound(a, n, key);
   return lo < n && a[lo] == key ? lo : NONE;
 }
 
@@ -158,20 +153,43 @@ __global__ __launch_bounds__(256) void k_lk_resolve(DevSnap s, const kg_lookup* 
     const uint32_t sn = nmap_find(s, x.sns, x.srel, x.sobj);
     subj = sn == NONE ? NONE : (SET_BIT | sn);
   }
-  int32_t d = x.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:68-70
-  const uint8_t rf = relflag(s, x.ns, x.rel);
-  const bool virt = s.virt && x.ns < s.n_ns && x.rel < s.n_rel && s.virt[(size_t)x.ns * s.n_rel + x.rel];
-  const uint32_t mode = (rf == 0 || virt) ? (s.radj ? LK_REVERSE : LK_NODES) : LK_ALL;
+  const uint32_t mode =
+      (relflag(s, x.ns, x.rel) == 0 || rel_is_union(s, x.ns, x.rel)) ? (s.radj ? LK_REVERSE : LK_NODES) : LK_ALL;
   uint2 h = make_uint2(0, 0);
   if (mode == LK_REVERSE) {
     h = holders_find(s, subj);
     if ((uint64_t)h.x + h.y > hold_n) h = make_uint2(0, 0);  // never read past hold[]
   }
-  lr[i] = LReq{subj, d, mode, h.x, h.y, 0};
+  lr[i] = LReq{subj, clamp_depth(x.max_depth, global), mode, h.x, h.y, 0};
 }
 
-// ------------------------------------------------------------------ the reverse walk
+// A resolved subject-lookup request.
+enum : uint32_t { LS_WALK = 0, LS_EMPTY = 1, LS_CONFIRM = 2 };
+struct SReq {
+  uint32_t root;  // root node (walk mode)
+  int32_t depth;  // clamped rest depth (>= 1)
+  uint32_t mode;  // LS_*
+  uint32_t pad;
+};
+
+// The subject-free part of k_resolve.  A relation without a rewrite or a materialised union: a missing
+// root answers every check NotMember (k_resolve routes it DONE), a pure root is walked, an impure one
+// confirmed.  Every other relation (interpreter, formula split, undeclared) is confirmed.
+__global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const kg_lookup_subj* __restrict__ q, uint32_t n,
+                                                    int32_t global, SReq* __restrict__ sr) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const kg_lookup_subj x = q[i];
+  uint32_t mode = LS_CONFIRM, root = NONE;
+  if (relflag(s, x.ns, x.rel) == 0 || rel_is_union(s, x.ns, x.rel)) {
+    root = nmap_find(s, x.ns, x.rel, x.obj);
+    if (root >= s.n_nodes) mode = LS_EMPTY;
+    else mode = (s.nflags && (s.nflags[root] & NF_IMPURE)) ? LS_CONFIRM : LS_WALK;
+  }
+  sr[i] = SReq{root, clamp_depth(x.max_depth, global), mode, 0};
+}
+
+// ------------------------------------------------------------------ the walk: arrivals and seeds
 // Request bits m arrive at node p.  Called by every lane of a wave (act: this lane has a node).  New
 // bits are recorded in vis / next (and returned), p joins the next frontier when it had no new bit yet
 // and the touched list when it had no bit at all.
@@ -189,40 +207,29 @@ __device__ __forceinline__ u64 lk_mark(const DevSnap& s, const Walk& W, bool act
   return nb;
 }
 
+// Every request whose bit is in `bits` lists id (request << 32 | id).  Called by every lane of a wave.
+__device__ __forceinline__ void lk_list(const Walk& W, u64 bits, uint32_t id) {
+  u64 at = wave_reserve64(&W.ctl->ocount, (uint32_t)__popcll(bits));
+  for (; bits; bits &= bits - 1, at++)
+    if (at < W.ocap) W.okeys[at] = ((u64)W.greq[__ffsll(bits) - 1].req << 32) | id;
+}
+
 // The reverse walk's arrival: every new bit whose request asks for p's (ns, rel) lists p's object if p is
 // pure.  Impure nodes are candidates of the confirmation (every ancestor of one is impure too).
 __device__ __forceinline__ void lk_visit(const DevSnap& s, const Walk& W, bool act, uint32_t p, u64 m) {
   const u64 nb = lk_mark(s, W, act, p, m);
-  uint32_t c = 0, pns = 0, prel = 0;
+  u64 want = 0;
   if (nb && !(s.nflags && (s.nflags[p] & NF_IMPURE))) {
-    pns = s.nd_ns[p];
-    prel = s.nd_rel[p];
+    const uint32_t pns = s.nd_ns[p], prel = s.nd_rel[p];
     for (u64 b = nb; b; b &= b - 1) {
       const GReq g = W.greq[__ffsll(b) - 1];
-      c += (g.ns == pns && g.rel == prel) ? 1u : 0u;
+      if (g.ns == pns && g.rel == prel) want |= b & -b;  // the lowest bit of b
     }
   }
-  uint32_t tot;
-  const uint32_t ex = wave_excl_scan(c, &tot);
-  if (tot) {
-    u64 base = 0;
-    if (lane_id() == 0) base = atomicAdd(&W.ctl->ocount, (u64)tot);
-    base = wave_bcast64(base, 0);
-    if (c) {
-      const uint32_t pobj = s.nd_obj[p];
-      u64 pos = base + ex;
-      for (u64 b = nb; b; b &= b - 1) {
-        const GReq g = W.greq[__ffsll(b) - 1];
-        if (g.ns == pns && g.rel == prel) {
-          if (pos < W.ocap) W.okeys[pos] = ((u64)g.req << 32) | pobj;
-          pos++;
-        }
-      }
-    }
-  }
+  lk_list(W, want, want ? s.nd_obj[p] : 0u);
 }
 
-// Level 0: one workgroup per request of the group strides over the subject's holders.
+// Reverse, level 0: one workgroup per request of the group strides over the subject's holders.
 __global__ __launch_bounds__(256) void k_lk_seed(DevSnap s, Walk W, const LReq* __restrict__ lr) {
   const uint32_t b = blockIdx.x;
   const LReq r = lr[W.greq[b].req];
@@ -234,30 +241,53 @@ __global__ __launch_bounds__(256) void k_lk_seed(DevSnap s, Walk W, const LReq* 
   }
 }
 
-// Before level j: every frontier node hands its new bits over (cmask, restricted to the requests
-// whose depth still reaches level j) and frees next[]; len = its parent row, 0 when nothing is left to
-// carry or the node is impure.  Thread F writes the sentinel and resets the list the level will build.
-__device__ __forceinline__ u64 lk_prep_one(const DevSnap& s, u64* next, const uint32_t* cur, u64* cmask, uint32_t i,
-                                           u64 live) {
-  const uint32_t v = cur[i];
-  u64 m = next[v];
-  next[v] = 0;
-  if (s.nflags && (s.nflags[v] & NF_IMPURE)) m = 0;
-  m &= live;
-  cmask[i] = m;
-  return m ? s.radj_off[v + 1] - s.radj_off[v] : 0ull;
+// Forward, level 0: bit b on the root of request b of the group.
+__global__ __launch_bounds__(64) void k_ls_seed(DevSnap s, Walk W, uint32_t gn) {
+  const uint32_t b = threadIdx.x;
+  const bool act = b < gn;
+  lk_mark(s, W, act, act ? W.greq[b].root : NONE, 1ull << b);
 }
 
-__global__ __launch_bounds__(256) void k_lk_prep(DevSnap s, u64* next, const uint32_t* __restrict__ cur, uint32_t F,
-                                                 u64 live, u64* __restrict__ cmask, u64* __restrict__ len,
-                                                 uint32_t* fcount_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < F) len[i] = lk_prep_one(s, next, cur, cmask, i, live);
-  else if (i == F) {
-    len[F] = 0;
-    *fcount_out = 0;
+// ------------------------------------------------------------------ the walk: one level
+// The frontier of level j: entry i is node cur[i] and carries the request bits cmask[i].
+struct Frontier {
+  const uint32_t* cur;
+  u64* cmask;
+  uint32_t F;
+};
+// One kind of row of the nodes: node v owns val[off[v], off[v + 1]) of val[0, n).
+struct Rows {
+  const uint64_t* off;
+  const uint32_t* val;
+  uint64_t n;
+};
+
+// Before level j, entry i's row length.  TAKE: the node first hands its new bits over (cmask[i],
+// restricted to live: the requests whose depth still reaches level j, D-1 >= j; none from an impure node)
+// and frees next[].  Forward, nflags == nullptr: everything a pure root reaches is pure, so no node flag
+// is read.  !TAKE: the bits cmask[i] holds, restricted to live.
+template <bool TAKE>
+struct RowLen {
+  Frontier f;
+  const uint64_t* off;
+  u64 live;
+  u64* next;
+  const uint8_t* nflags;
+  __device__ u64 operator()(uint32_t i) const {
+    const uint32_t v = f.cur[i];
+    u64 m;
+    if (TAKE) {
+      m = next[v] & live;
+      next[v] = 0;
+      if (nflags && (nflags[v] & NF_IMPURE)) m = 0;
+      f.cmask[i] = m;
+    } else m = f.cmask[i] & live;
+    return m ? off[v + 1] - off[v] : 0ull;
   }
-}
+};
+struct NoLen {
+  uint32_t none;  // a kernel argument: not an empty struct
+};
 
 // One workgroup of 256: pref[i] = the sum of f(0 .. i - 1) for i in [0, F]; thread t calls f(i) for
 // i = t, t + 256, ...
@@ -290,38 +320,72 @@ __device__ __forceinline__ void lk_block_prefix(uint32_t F, u64* __restrict__ pr
   if (threadIdx.x == 0) pref[F] = carry;
 }
 
-// k_lk_prep with the prefix in the launch, for frontiers one workgroup scans in a few steps.
-__global__ __launch_bounds__(256) void k_lk_prep_scan(DevSnap s, u64* next, const uint32_t* __restrict__ cur,
-                                                      uint32_t F, u64 live, u64* __restrict__ cmask,
-                                                      u64* __restrict__ pref, uint32_t* fcount_out) {
-  lk_block_prefix(F, pref, [&](uint32_t i) { return lk_prep_one(s, next, cur, cmask, i, live); });
+// Frontiers one workgroup scans in a few steps (F <= PREFIX_IN_KERNEL): the lengths and their prefix in
+// one launch, of both kinds of row for the forward walk (LenB = NoLen: of one).  The second prefix reads
+// the cmask[i] that the same thread wrote during the first.  Resets the list the level will build.
+constexpr uint32_t PREFIX_IN_KERNEL = 4096;
+template <class LenA, class LenB>
+__global__ __launch_bounds__(256) void k_lk_prep_scan(uint32_t F, LenA len_a, u64* __restrict__ pref_a, LenB len_b,
+                                                      u64* __restrict__ pref_b, uint32_t* fcount_out) {
+  lk_block_prefix(F, pref_a, len_a);
+  if constexpr (!std::is_same<LenB, NoLen>::value) lk_block_prefix(F, pref_b, len_b);
   if (threadIdx.x == 0) *fcount_out = 0;
 }
+// Larger frontiers: one launch per kind of row writes the lengths, hipcub scans them.  Thread F writes
+// the sentinel and (fcount_out: the level's first prepare) resets the list the level will build.
+template <class Len>
+__global__ __launch_bounds__(256) void k_lk_prep(uint32_t F, Len len_of, u64* __restrict__ len, uint32_t* fcount_out) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < F) len[i] = len_of(i);
+  else if (i == F) {
+    len[F] = 0;
+    if (fcount_out) *fcount_out = 0;
+  }
+}
 
-// Level j: one lane per reverse edge of the frontier (owner search in the prefix of the row lengths).
-__global__ __launch_bounds__(256) void k_lk_level(DevSnap s, Walk W, const uint32_t* __restrict__ cur,
-                                                  const u64* __restrict__ cmask, const u64* __restrict__ pref,
-                                                  uint32_t F, uint64_t n_edges) {
-  const u64 total = pref[F];
-  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&W.ctl->edges, total);
+// The level: one lane per entry of the frontier's rows (owner search in the prefix of the row lengths).
+// Every lane of a wave calls body(v, m) -- v: the entry, m: its owner's bits; NONE, 0: the lane has none.
+template <class Body>
+__global__ __launch_bounds__(256) void k_lk_frontier_edges(Frontier f, Rows r, const u64* __restrict__ pref, LkCtl* ctl,
+                                                           Body body) {
+  const u64 total = pref[f.F];
+  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&ctl->edges, total);
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < total; base += stride) {
     const u64 e = base + lane_id();
-    bool act = e < total;
-    uint32_t p = NONE;
+    uint32_t v = NONE;
     u64 m = 0;
-    if (act) {
-      const uint32_t own = csr_owner((const uint64_t*)pref, F, e);
-      const u64 idx = s.radj_off[cur[own]] + (e - pref[own]);
-      act = idx < n_edges;
-      if (act) {
-        p = s.radj[idx];
-        m = cmask[own];
+    if (e < total) {
+      const uint32_t own = csr_owner((const uint64_t*)pref, f.F, e);
+      const u64 idx = r.off[f.cur[own]] + (e - pref[own]);
+      if (idx < r.n) {
+        v = r.val[idx];
+        m = f.cmask[own];
       }
     }
-    lk_visit(s, W, act, p, m);
+    body(v, m);
   }
 }
+
+// One hop over radj (reverse: every bit, and the arrival lists the node's object) or adj (forward: the
+// bits that go one level further, xlive: D-1 >= j+1, and the arrival only marks).
+template <bool LIST>
+struct Hop {
+  DevSnap s;
+  Walk W;
+  u64 on;
+  __device__ void operator()(uint32_t p, u64 m) const {
+    if (LIST) lk_visit(s, W, true, p, m & on);
+    else lk_mark(s, W, true, p, m & on);
+  }
+};
+// The forward walk's emit over the check rows.  An untagged entry is a subject id every request bit of
+// its node lists (request << 32 | id); subject sets -- `...` ones included -- are skipped.  An id the
+// check maps to no subject (>= 2^31 - 1, k_resolve) is never a member.
+struct EmitIds {
+  Walk W;
+  __device__ void operator()(uint32_t sub, u64 m) const { lk_list(W, sub < 0x7FFFFFFFu ? m : 0ull, sub); }
+};
 
 // After a group: the masks of every touched node back to 0, the node lists empty.
 __global__ __launch_bounds__(256) void k_lk_clear(u64* vis, u64* next, const uint32_t* __restrict__ touched,
@@ -338,150 +402,7 @@ __global__ void k_lk_lists_reset(LkCtl* ctl) {
   ctl->tcount = 0;
 }
 
-// ------------------------------------------------------------------ the forward walk (subject lookup)
-// A resolved subject-lookup request.
-enum : uint32_t { LS_WALK = 0, LS_EMPTY = 1, LS_CONFIRM = 2 };
-struct SReq {
-  uint32_t root;  // root node (walk mode)
-  int32_t depth;  // clamped rest depth (>= 1)
-  uint32_t mode;  // LS_*
-  uint32_t pad;
-};
-
-// The subject-free part of k_resolve.  A relation without a rewrite or a materialised union: a missing
-// root answers every check NotMember (k_resolve routes it DONE), a pure root is walked, an impure one
-// confirmed.  Every other relation (interpreter, formula split, undeclared) is confirmed.
-__global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const kg_lookup_subj* __restrict__ q, uint32_t n,
-                                                    int32_t global, SReq* __restrict__ sr) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const kg_lookup_subj x = q[i];
-  int32_t d = x.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:68-70
-  const uint8_t rf = relflag(s, x.ns, x.rel);
-  const bool virt = s.virt && x.ns < s.n_ns && x.rel < s.n_rel && s.virt[(size_t)x.ns * s.n_rel + x.rel];
-  uint32_t mode = LS_CONFIRM, root = NONE;
-  if (rf == 0 || virt) {
-    root = nmap_find(s, x.ns, x.rel, x.obj);
-    if (root >= s.n_nodes) mode = LS_EMPTY;
-    else mode = (s.nflags && (s.nflags[root] & NF_IMPURE)) ? LS_CONFIRM : LS_WALK;
-  }
-  sr[i] = SReq{root, d, mode, 0};
-}
-
-// Level 0: bit b on the root of request b of the group.
-__global__ __launch_bounds__(64) void k_ls_seed(DevSnap s, Walk W, uint32_t gn) {
-  const uint32_t b = threadIdx.x;
-  const bool act = b < gn;
-  lk_mark(s, W, act, act ? W.greq[b].root : NONE, 1ull << b);
-}
-
-// Before level j: every frontier node hands its new bits over (cmask, restricted to the requests whose
-// depth still probes level j: D-1 >= j) and frees next[].  Two row lengths per node: its check row, whose
-// subject ids the level lists, and -- for the bits that go one level further (xlive: D-1 >= j+1) -- its
-// adj row.  Everything a pure root reaches is pure, so no node flag is read.
-__device__ __forceinline__ u64 ls_prep_one(const uint64_t* coff, u64* next, const uint32_t* cur, u64* cmask,
-                                           uint32_t i, u64 live) {
-  const uint32_t v = cur[i];
-  const u64 m = next[v] & live;
-  next[v] = 0;
-  cmask[i] = m;
-  return m ? coff[v + 1] - coff[v] : 0ull;
-}
-__device__ __forceinline__ u64 ls_adj_one(const DevSnap& s, const uint32_t* cur, const u64* cmask, uint32_t i,
-                                          u64 xlive) {
-  const uint32_t v = cur[i];
-  return (cmask[i] & xlive) ? s.adj_off[v + 1] - s.adj_off[v] : 0ull;
-}
-
-// Frontiers one workgroup scans in a few steps: both prefixes in one launch (check rows -> epref, adj
-// rows -> apref).
-__global__ __launch_bounds__(256) void k_ls_prep_scan(DevSnap s, const uint64_t* __restrict__ coff, u64* next,
-                                                      const uint32_t* __restrict__ cur, uint32_t F, u64 live,
-                                                      u64 xlive, u64* cmask, u64* __restrict__ epref,
-                                                      u64* __restrict__ apref, uint32_t* fcount_out) {
-  lk_block_prefix(F, epref, [&](uint32_t i) { return ls_prep_one(coff, next, cur, cmask, i, live); });
-  lk_block_prefix(F, apref, [&](uint32_t i) { return ls_adj_one(s, cur, cmask, i, xlive); });  // i: this thread's own cmask
-  if (threadIdx.x == 0) *fcount_out = 0;
-}
-// Larger frontiers: one launch per kind of row writes the lengths, hipcub scans them.
-__global__ __launch_bounds__(256) void k_ls_prep(const uint64_t* __restrict__ coff, u64* next,
-                                                 const uint32_t* __restrict__ cur, uint32_t F, u64 live,
-                                                 u64* __restrict__ cmask, u64* __restrict__ len, uint32_t* fcount_out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < F) len[i] = ls_prep_one(coff, next, cur, cmask, i, live);
-  else if (i == F) {
-    len[F] = 0;
-    *fcount_out = 0;
-  }
-}
-__global__ __launch_bounds__(256) void k_ls_prep_adj(DevSnap s, const uint32_t* __restrict__ cur, uint32_t F, u64 xlive,
-                                                     const u64* __restrict__ cmask, u64* __restrict__ len) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < F) len[i] = ls_adj_one(s, cur, cmask, i, xlive);
-  else if (i == F) len[F] = 0;
-}
-
-// Level j, emit: one lane per check-row entry of the frontier.  An untagged entry is a subject id every
-// request bit of its node lists (request << 32 | id); subject sets -- `...` ones included -- are skipped.
-// An id the check maps to no subject (>= 2^31 - 1, k_resolve) is never a member.
-__global__ __launch_bounds__(256) void k_ls_emit(Walk W, const uint64_t* __restrict__ coff,
-                                                 const uint32_t* __restrict__ csub, const uint32_t* __restrict__ cur,
-                                                 const u64* __restrict__ cmask, const u64* __restrict__ pref, uint32_t F,
-                                                 uint64_t n_rows) {
-  const u64 total = pref[F];
-  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&W.ctl->edges, total);
-  const u64 stride = (u64)gridDim.x * 256;
-  for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < total; base += stride) {
-    const u64 e = base + lane_id();
-    uint32_t sub = NONE;
-    u64 m = 0;
-    if (e < total) {
-      const uint32_t own = csr_owner((const uint64_t*)pref, F, e);
-      const u64 idx = coff[cur[own]] + (e - pref[own]);
-      if (idx < n_rows) {
-        sub = csub[idx];
-        m = cmask[own];
-      }
-    }
-    const uint32_t c = sub < 0x7FFFFFFFu ? (uint32_t)__popcll(m) : 0u;
-    uint32_t tot;
-    const uint32_t ex = wave_excl_scan(c, &tot);
-    if (!tot) continue;
-    u64 at = 0;
-    if (lane_id() == 0) at = atomicAdd(&W.ctl->ocount, (u64)tot);
-    at = wave_bcast64(at, 0) + ex;
-    for (u64 b = c ? m : 0ull; b; b &= b - 1, at++)
-      if (at < W.ocap) W.okeys[at] = ((u64)W.greq[__ffsll(b) - 1].req << 32) | sub;
-  }
-}
-
-// Level j, expand: one lane per adj edge of the frontier; the bits that go one level further arrive at
-// the child.
-__global__ __launch_bounds__(256) void k_ls_expand(DevSnap s, Walk W, const uint32_t* __restrict__ cur,
-                                                   const u64* __restrict__ cmask, const u64* __restrict__ pref,
-                                                   uint32_t F, u64 xlive, uint64_t n_edges) {
-  const u64 total = pref[F];
-  if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&W.ctl->edges, total);
-  const u64 stride = (u64)gridDim.x * 256;
-  for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < total; base += stride) {
-    const u64 e = base + lane_id();
-    bool act = e < total;
-    uint32_t c = NONE;
-    u64 m = 0;
-    if (act) {
-      const uint32_t own = csr_owner((const uint64_t*)pref, F, e);
-      const u64 idx = s.adj_off[cur[own]] + (e - pref[own]);
-      act = idx < n_edges;
-      if (act) {
-        c = s.adj[idx];
-        m = cmask[own] & xlive;
-      }
-    }
-    lk_mark(s, W, act, c, m);
-  }
-}
-
+// ------------------------------------------------------------------ candidates of a subject lookup
 // The domain of the confirmation: the subject ids that occur in a tuple.  The holder bitmap has exactly
 // these ids; without it the untagged entries of the check rows are listed (sorted and deduplicated next).
 __global__ __launch_bounds__(256) void k_ls_dom_bits(const uint32_t* __restrict__ hbits, uint32_t nbits, uint32_t* dom,
@@ -492,12 +413,7 @@ __global__ __launch_bounds__(256) void k_ls_dom_bits(const uint32_t* __restrict_
     const uint32_t wi = base + lane_id();
     uint32_t bits = wi < words ? hbits[wi] : 0u;
     if (wi == words - 1 && (nbits & 31)) bits &= (1u << (nbits & 31)) - 1;
-    uint32_t tot;
-    const uint32_t ex = wave_excl_scan((uint32_t)__popc(bits), &tot);
-    if (!tot) continue;
-    u64 at = 0;
-    if (lane_id() == 0) at = atomicAdd(&ctl->dcount, (u64)tot);
-    at = wave_bcast64(at, 0) + ex;
+    u64 at = wave_reserve64(&ctl->dcount, (uint32_t)__popc(bits));
     for (; bits; bits &= bits - 1, at++)
       if (at < dcap) dom[at] = wi * 32 + (__ffs(bits) - 1);
   }
@@ -508,13 +424,7 @@ __global__ __launch_bounds__(256) void k_ls_dom_rows(const uint32_t* __restrict_
   for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n_rows; base += stride) {
     const u64 i = base + lane_id();
     const uint32_t sub = i < n_rows ? csub[i] : NONE;
-    const bool pred = !(sub & SET_BIT);
-    const uint64_t m = __ballot(pred);
-    if (!m) continue;
-    u64 at = 0;
-    if (lane_id() == 0) at = atomicAdd(&ctl->dcount, (u64)__popcll(m));
-    at = wave_bcast64(at, 0) + lanes_below(m);
-    if (pred && at < dcap) dom[at] = sub;
+    lk_append64(!(sub & SET_BIT), sub, dom, &ctl->dcount, dcap);
   }
 }
 
@@ -538,17 +448,12 @@ __global__ __launch_bounds__(256) void k_ls_cands(const uint32_t* __restrict__ d
   }
 }
 
-// ------------------------------------------------------------------ candidates
+// ------------------------------------------------------------------ candidates of an object lookup
 // c candidate checks of object obj, one per request of reqs[0, c).  Called by every lane of a wave.
 __device__ __forceinline__ void lk_emit_cands(uint32_t c, const uint32_t* reqs, uint32_t obj,
                                               const kg_lookup* __restrict__ q, kg_query* cq, uint32_t* creq, u64 ccap,
                                               LkCtl* ctl) {
-  uint32_t tot;
-  const uint32_t ex = wave_excl_scan(c, &tot);
-  if (!tot) return;
-  u64 base = 0;
-  if (lane_id() == 0) base = atomicAdd(&ctl->ccount, (u64)tot);
-  base = wave_bcast64(base, 0) + ex;
+  const u64 base = wave_reserve64(&ctl->ccount, c);
   for (uint32_t t = 0; t < c; t++) {
     const u64 pos = base + t;
     if (pos >= ccap) break;
@@ -574,10 +479,10 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
       const uint32_t ns = s.nd_ns[v], rel = s.nd_rel[v];
       obj = s.nd_obj[v];
       if (T.K) {
-        k = lk_find64(T.keys, T.K, ((u64)ns << 32) | rel);
+        k = lk_find(T.keys, T.K, ((u64)ns << 32) | rel);
         if (k != NONE && (T.kall[k] || (s.nflags && (s.nflags[v] & NF_IMPURE)))) c = T.koff[k + 1] - T.koff[k];
       }
-      if (T.M) slot = lk_find32(T.nsv, T.M, ns);
+      if (T.M) slot = lk_find(T.nsv, T.M, ns);
     }
     lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
     lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
@@ -643,31 +548,19 @@ __global__ __launch_bounds__(256) void k_lk_finish(const u64* __restrict__ uk, u
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < m || i <= n_reqs; i += stride) {
     if (i < m) objs[i] = (uint32_t)uk[i];
-    if (i <= n_reqs) {  // first key of request i or later
-      const u64 key = i << 32;
-      u64 lo = 0, hi = m;
-      while (lo < hi) {
-        const u64 mid = (lo + hi) >> 1;
-        if (uk[mid] < key) lo = mid + 1;
-        else hi = mid;
-      }
-      req_off[i] = lo;
+    if (i <= n_reqs) {
+      req_off[i] = lk_lower_bound(uk, m, i << 32);  // first key of request i or later
       if (i < n_reqs) err_code[i] = errmin[i] == ~0ull ? 0u : (uint32_t)errmin[i];
     }
   }
 }
 
+// ------------------------------------------------------------------ host: a lane's buffers, one call
 // The device buffers of lookups on one lane, kept between calls.
 struct LookupBufs {
-  PinBuf<kg_lookup> h_req;
-  DevBuf<kg_lookup> d_req;
-  DevBuf<LReq> d_lr;
-  PinBuf<LReq> h_lr;
-  // the same of a subject lookup
-  PinBuf<kg_lookup_subj> h_sreq;
-  DevBuf<kg_lookup_subj> d_sreq;
-  DevBuf<SReq> d_sr;
-  PinBuf<SReq> h_sr;
+  // the call's requests and what its resolve kernel made of them (bytes): a lane runs one call at a time
+  PinBuf<void> h_req, h_res;
+  DevBuf<void> d_req, d_res;
   DevBuf<uint32_t> dom, dom2;  // subject ids of the confirmation's domain
   DevBuf<LkCtl> ctl;
   // walk
@@ -695,354 +588,118 @@ struct LookupBufs {
   }
 };
 
-template <class T>
-int grow_keep(DevBuf<T>& b, size_t n, size_t keep, hipStream_t st) {
-  if (n <= b.cap()) return 0;
-  DevBuf<T> nb;
-  HIPC(nb.reserve(n));
-  if (keep) HIPC(hipMemcpyAsync(nb.get(), b.get(), keep * sizeof(T), hipMemcpyDeviceToDevice, st));
-  HIPC(hipStreamSynchronize(st));
-  b = std::move(nb);
-  return 0;
-}
-
-int read_ctl(Workspace* w, LookupBufs& B, hipStream_t st, LkCtl* h) {
-  void* hb = w->host_buf(65536);
-  if (!hb) return set_error(-1, "pinned host buffer");
-  HIPC(hipMemcpyAsync(hb, B.ctl.get(), sizeof(LkCtl), hipMemcpyDeviceToHost, st));
-  if (int rc = w->wait(st, true)) return rc;
-  memcpy(h, hb, sizeof(LkCtl));
-  return 0;
-}
-
-// The start of a call: the timing events, the counters and the per-request error words, all cleared.
-int lk_begin(LookupBufs& B, size_t n, hipStream_t st) {
-  if (!B.ev[0])
-    for (auto& e : B.ev) HIPC(hipEventCreate(&e));
-  HIPC(B.ctl.reserve(1));
-  HIPC(B.n_errors.reserve(n));
-  HIPC(B.errmin.reserve(n));
-  HIPC(hipEventRecord(B.ev[0], st));
-  HIPC(hipMemsetAsync(B.ctl.get(), 0, sizeof(LkCtl), st));
-  HIPC(hipMemsetAsync(B.n_errors.get(), 0, n * 8, st));
-  HIPC(hipMemsetAsync(B.errmin.get(), 0xFF, n * 8, st));
-  return 0;
-}
-
-// The walk buffers of a lane (both walks use them): allocated for nn nodes on first use, the masks all
-// clear on return, the group's request bits on the device.  *scan_bytes: hipcub's scan temporaries.
-int walk_reserve(LookupBufs& B, uint32_t nn, const std::vector<GReq>& greq, hipStream_t st, size_t* scan_bytes) {
-  if (B.walk_nodes < nn) {
-    B.walk_nodes = 0;
-    HIPC(B.vis.reserve(nn));
-    HIPC(B.next.reserve(nn));
-    HIPC(B.cmask.reserve(nn));
-    HIPC(B.len.reserve((size_t)nn + 1));
-    HIPC(B.pref.reserve((size_t)nn + 1));
-    HIPC(B.fl[0].reserve(nn));
-    HIPC(B.fl[1].reserve(nn));
-    HIPC(B.touched.reserve(nn));
-    B.walk_nodes = nn;
-    B.dirty = true;
-  }
-  if (B.dirty) {
-    HIPC(hipMemsetAsync(B.vis.get(), 0, (size_t)B.walk_nodes * 8, st));
-    HIPC(hipMemsetAsync(B.next.get(), 0, (size_t)B.walk_nodes * 8, st));
-    B.dirty = false;
-  }
-  HIPC(B.greq.reserve(greq.size()));
-  HIPC(hipMemcpyAsync(B.greq.get(), greq.data(), greq.size() * sizeof(GReq), hipMemcpyHostToDevice, st));
-  HIPC(hipStreamSynchronize(st));  // greq is pageable
-  *scan_bytes = 0;
-  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, *scan_bytes, B.len.get(), B.pref.get(), (size_t)nn + 1, st));
-  HIPC(B.tmp.reserve(*scan_bytes + 16));
-  return 0;
-}
-
-// After a group: the masks cleared by replaying the touched list, the node lists empty.  h: the
-// counters as the group's last launch left them.
-int walk_finish(Snapshot* s, LookupBufs& B, hipStream_t st, const LkCtl& h) {
-  hipLaunchKernelGGL(k_lk_clear, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, st, B.vis.get(), B.next.get(),
-                     (const uint32_t*)B.touched.get(), B.walk_nodes, B.ctl.get());
-  hipLaunchKernelGGL(k_lk_lists_reset, dim3(1), dim3(1), 0, st, B.ctl.get());
-  HIPC(hipGetLastError());
-  HIPC(hipStreamSynchronize(st));
-  B.dirty = h.over != 0;  // an overflowed touched list did not name every node to clear
-  if (h.over) return set_error(KG_ERR_RESOURCE_CODE, "lookup: a node list overflowed");
-  return 0;
-}
-
-// The output keys of a call (request << 32 | id).  The list grows when a step's true count passes it;
-// the step is then rerun.
-struct OutKeys {
-  LookupBufs& B;
+// One lookup call on a lane: what its steps need, and the start and the end both lookups share.
+struct Call {
+  Snapshot* s;
   Workspace* w;
   hipStream_t st;
-  u64 cap = 0;
-  u64 have = 0;  // keys of the finished steps
-  int init(const Snapshot* s) {
-    cap = s->lookup_cap ? s->lookup_cap : std::max<u64>(65536, B.okeys.cap());
-    HIPC(B.okeys.reserve((size_t)cap));
+  LookupBufs& B;
+  // The output keys (request << 32 | id): `have` of the finished steps in a list of `cap`.  The list
+  // grows when a step's true count passes it; the step is then rerun.
+  struct OutKeys {
+    u64 cap = 0, have = 0;
+  } O;
+  uint32_t grid_wide;
+  int32_t gmax;
+  size_t n = 0;
+  u64 n_exact = 0, n_cand = 0, n_conf = 0;
+  uint64_t st_edges = 0, st_levels = 0;
+
+  Call(Snapshot* s_, Lane* L, int32_t gmax_)
+      : s(s_), w(L->w), st(L->stream), B(*static_cast<LookupBufs*>(L->lk ? L->lk : (L->lk = new LookupBufs()))),
+        grid_wide((uint32_t)s_->n_cu * 4), gmax(gmax_ < 1 ? 5 : gmax_) {}  // as check_batch_begin
+
+  // The start: the requests staged through pinned memory, the timing events, the counters and the
+  // per-request error words cleared, the requests resolved (resolve() launches the kernel) and read back.
+  template <class Req, class Res, class Resolve>
+  int begin(const Req* reqs, size_t n_reqs, const Res** res, Resolve resolve) {
+    n = n_reqs;
+    if (n > 0x7FFFFFFFull) return set_error(-2, "batch too large");
+    HIPC(hipSetDevice(s->device));
+    HIPC(B.h_req.reserve(n * sizeof(Req)));
+    HIPC(B.d_req.reserve(n * sizeof(Req)));
+    HIPC(B.d_res.reserve(n * sizeof(Res)));
+    HIPC(B.h_res.reserve(n * sizeof(Res)));
+    memcpy(B.h_req.get(), reqs, n * sizeof(Req));
+    if (!B.ev[0])
+      for (auto& e : B.ev) HIPC(hipEventCreate(&e));
+    HIPC(B.ctl.reserve(1));
+    HIPC(B.n_errors.reserve(n));
+    HIPC(B.errmin.reserve(n));
+    HIPC(hipEventRecord(B.ev[0], st));
+    HIPC(hipMemsetAsync(B.ctl.get(), 0, sizeof(LkCtl), st));
+    HIPC(hipMemsetAsync(B.n_errors.get(), 0, n * 8, st));
+    HIPC(hipMemsetAsync(B.errmin.get(), 0xFF, n * 8, st));
+    HIPC(hipMemcpyAsync(B.d_req.get(), B.h_req.get(), n * sizeof(Req), hipMemcpyHostToDevice, st));
+    resolve((uint32_t)((n + 255) / 256), (const Req*)B.d_req.get(), (Res*)B.d_res.get());
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(B.h_res.get(), B.d_res.get(), n * sizeof(Res), hipMemcpyDeviceToHost, st));
+    if (int rc = w->wait(st, true)) return rc;
+    *res = (const Res*)B.h_res.get();
+    O.cap = s->lookup_cap ? s->lookup_cap : std::max<u64>(65536, B.okeys.cap());
+    HIPC(B.okeys.reserve((size_t)O.cap));
     return 0;
   }
+
   // a list of at least `need` keys that keeps the finished steps', and the device counter back at them
-  int regrow(u64 need) {
-    cap = std::max<u64>(need, 2 * cap);
-    if (int rc = grow_keep(B.okeys, (size_t)cap, (size_t)have, st)) return rc;
+  int regrow_out(u64 need) {
+    O.cap = std::max<u64>(need, 2 * O.cap);
+    if (O.cap > B.okeys.cap()) {
+      DevBuf<u64> nb;
+      HIPC(nb.reserve((size_t)O.cap));
+      if (O.have) HIPC(hipMemcpyAsync(nb.get(), B.okeys.get(), (size_t)O.have * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(hipStreamSynchronize(st));
+      B.okeys = std::move(nb);
+    }
     void* hb = w->host_buf(65536);
     if (!hb) return set_error(-1, "pinned host buffer");
-    memcpy(hb, &have, 8);
+    memcpy(hb, &O.have, 8);
     HIPC(hipMemcpyAsync(&B.ctl.get()->ocount, hb, 8, hipMemcpyHostToDevice, st));
     HIPC(hipStreamSynchronize(st));  // the pinned word is reused by the next readback
     return 0;
   }
-};
 
-// The candidates' answers join the output keys (k_lk_collect); errors are counted on the first pass only.
-template <bool SUBJ>
-int collect(Snapshot* s, Workspace* w, LookupBufs& B, hipStream_t st, u64 n_cand, OutKeys& O, u64* n_conf) {
-  for (int pass = 0;; pass++) {
-    hipLaunchKernelGGL(k_lk_collect<SUBJ>, dim3((uint32_t)std::min<u64>((u64)s->n_cu * 4, n_cand / 256 + 1)), dim3(256),
-                       0, st, (const kg_query*)B.cq.get(), (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(),
-                       (const uint32_t*)B.cerr.get(), n_cand, B.okeys.get(), O.cap, pass == 0 ? 1 : 0, B.n_errors.get(),
-                       B.errmin.get(), B.ctl.get());
-    HIPC(hipGetLastError());
-    LkCtl h;
-    if (int rc = read_ctl(w, B, st, &h)) return rc;
-    if (h.ocount > O.cap) {
-      if (pass) return set_error(KG_ERR_RESOURCE_CODE, "lookup: output list overflowed twice");
-      if (int rc = O.regrow(h.ocount)) return rc;
-      continue;
-    }
-    O.have = h.ocount;
-    *n_conf = h.confirmed;
+  int read_ctl(LkCtl* h) {
+    void* hb = w->host_buf(65536);
+    if (!hb) return set_error(-1, "pinned host buffer");
+    HIPC(hipMemcpyAsync(hb, B.ctl.get(), sizeof(LkCtl), hipMemcpyDeviceToHost, st));
+    if (int rc = w->wait(st, true)) return rc;
+    memcpy(h, hb, sizeof(LkCtl));
     return 0;
   }
-}
 
-// The end of a call: the keys sorted, duplicates dropped, split by request, and the four output arrays
-// in one pinned block.
-int lk_output(Snapshot* s, Workspace* w, LookupBufs& B, hipStream_t st, size_t n, u64 o_have, kg_lookup_buf* out);
+  // The end: the keys sorted, duplicates dropped, split by request, the output arrays in one pinned block.
+  int finish(kg_lookup_buf* out);
+};
 
-}  // namespace
-
-void lookup_bufs_free(void* p) { delete static_cast<LookupBufs*>(p); }
-
-// Runs on lane L (its stream and workspace; the caller holds the workspace's mutex).
-int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
-  if (gmax < 1) gmax = 5;  // as check_batch_begin
-  if (n > 0x7FFFFFFFull) return set_error(-2, "batch too large");
-  HIPC(hipSetDevice(s->device));
-  hipStream_t st = L->stream;
-  Workspace* w = L->w;
-  if (!L->lk) L->lk = new LookupBufs();
-  LookupBufs& B = *static_cast<LookupBufs*>(L->lk);
-  const DevSnap& ds = s->ds;
-  const uint32_t nn = ds.n_nodes;
-  const uint32_t grid_wide = (uint32_t)s->n_cu * 4;
-  HIPC(B.h_req.reserve(n));
-  HIPC(B.d_req.reserve(n));
-  HIPC(B.d_lr.reserve(n));
-  HIPC(B.h_lr.reserve(n));
-  memcpy(B.h_req.get(), reqs, n * sizeof(kg_lookup));
-  if (int rc = lk_begin(B, n, st)) return rc;
-  HIPC(hipMemcpyAsync(B.d_req.get(), B.h_req.get(), n * sizeof(kg_lookup), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_lk_resolve, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, ds, B.d_req.get(), (uint32_t)n,
-                     gmax, (uint64_t)s->n_check_rows, B.d_lr.get());
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(B.h_lr.get(), B.d_lr.get(), n * sizeof(LReq), hipMemcpyDeviceToHost, st));
-  if (int rc = w->wait(st, true)) return rc;
-  const LReq* lr = B.h_lr.get();
-
-  // ---- plan: walk groups and candidate tables
-  std::vector<GReq> greq;
-  std::map<u64, std::vector<uint32_t>> by_key;
-  std::map<uint32_t, std::vector<uint32_t>> by_ns;
-  for (size_t i = 0; i < n; i++) {
-    if (lr[i].mode == LK_ALL) {
-      by_ns[reqs[i].ns].push_back((uint32_t)i);
-      continue;
-    }
-    if (lr[i].mode == LK_REVERSE && lr[i].hcount) greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0});
-    // candidates of a reverse request: impure nodes -- none without node flags
-    if (lr[i].mode == LK_NODES || ds.nflags) by_key[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
-  }
-
-  OutKeys O{B, w, st};
-  if (int rc = O.init(s)) return rc;
-  uint64_t st_edges = 0, st_levels = 0;
-
-  // ---- the reverse walk, 64 requests per group
-  if (!greq.empty()) {
-    size_t scan_bytes = 0;
-    if (int rc = walk_reserve(B, nn, greq, st, &scan_bytes)) return rc;
-    for (size_t g0 = 0; g0 < greq.size();) {
-      const uint32_t gn = (uint32_t)std::min<size_t>(64, greq.size() - g0);
-      int32_t max_d = 1;
-      for (uint32_t b = 0; b < gn; b++) max_d = std::max(max_d, lr[greq[g0 + b].req].depth);
-      Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), O.cap,
-             B.greq.get() + g0, B.ctl.get()};
-      B.dirty = true;
-      hipLaunchKernelGGL(k_lk_seed, dim3(gn), dim3(256), 0, st, ds, W, (const LReq*)B.d_lr.get());
-      HIPC(hipGetLastError());
-      LkCtl h;
-      if (int rc = read_ctl(w, B, st, &h)) return rc;
-      uint32_t cur = 0, F = std::min(h.fcount[0], B.walk_nodes);
-      for (int32_t j = 1; j <= max_d - 1 && F; j++) {
-        u64 live = 0;  // requests whose depth reaches level j
-        for (uint32_t b = 0; b < gn; b++)
-          if (lr[greq[g0 + b].req].depth - 1 >= j) live |= 1ull << b;
-        W.fout = B.fl[cur ^ 1].get();
-        W.fsel = cur ^ 1;
-        uint32_t* fc_out = &B.ctl.get()->fcount[cur ^ 1];
-        if (F <= 4096) {
-          hipLaunchKernelGGL(k_lk_prep_scan, dim3(1), dim3(256), 0, st, ds, B.next.get(), (const uint32_t*)B.fl[cur].get(),
-                             F, live, B.cmask.get(), B.pref.get(), fc_out);
-        } else {
-          hipLaunchKernelGGL(k_lk_prep, dim3(F / 256 + 1), dim3(256), 0, st, ds, B.next.get(),
-                             (const uint32_t*)B.fl[cur].get(), F, live, B.cmask.get(), B.len.get(), fc_out);
-          HIPC(hipcub::DeviceScan::ExclusiveSum(B.tmp.get(), scan_bytes, B.len.get(), B.pref.get(), (size_t)F + 1, st));
-        }
-        hipLaunchKernelGGL(k_lk_level, dim3(grid_wide), dim3(256), 0, st, ds, W, (const uint32_t*)B.fl[cur].get(),
-                           (const u64*)B.cmask.get(), (const u64*)B.pref.get(), F, (uint64_t)s->n_set_edges);
-        HIPC(hipGetLastError());
-        if (int rc = read_ctl(w, B, st, &h)) return rc;
-        cur ^= 1;
-        F = std::min(h.fcount[cur], B.walk_nodes);
-        st_levels++;
-      }
-      if (int rc = walk_finish(s, B, st, h)) return rc;
-      if (h.ocount > O.cap) {  // the group's keys did not fit: a larger list, the group again
-        if (int rc = O.regrow(h.ocount)) return rc;
-        continue;
-      }
-      O.have = h.ocount;
-      st_edges = h.edges;  // summed on the device over every run, reruns included
-      g0 += gn;
-    }
-  }
-  const u64 n_exact = O.have;
-
-  // ---- candidates: one pass over the nodes, then the sorted domains of the confirm-all namespaces
-  u64 n_cand = 0, n_conf = 0;
-  if (!by_key.empty() || !by_ns.empty()) {
-    std::vector<uint32_t> blob;
-    const uint32_t K = (uint32_t)by_key.size(), M = (uint32_t)by_ns.size();
-    // layout (u32 words): keys[2K] | kall[K] | koff[K+1] | kreq[..] | nsv[M] | nsoff[M+1] | nsreq[..]
-    std::vector<u64> keys;
-    std::vector<uint32_t> kall, koff{0}, kreq, nsv, nsoff{0}, nsreq;
-    for (auto& kv : by_key) {
-      keys.push_back(kv.first);
-      kall.push_back(lr[kv.second[0]].mode == LK_NODES ? 1u : 0u);
-      kreq.insert(kreq.end(), kv.second.begin(), kv.second.end());
-      koff.push_back((uint32_t)kreq.size());
-    }
-    for (auto& kv : by_ns) {
-      nsv.push_back(kv.first);
-      nsreq.insert(nsreq.end(), kv.second.begin(), kv.second.end());
-      nsoff.push_back((uint32_t)nsreq.size());
-    }
-    blob.resize(2 * (size_t)K);
-    if (K) memcpy(blob.data(), keys.data(), (size_t)K * 8);
-    size_t o_kall = blob.size();
-    blob.insert(blob.end(), kall.begin(), kall.end());
-    size_t o_koff = blob.size();
-    blob.insert(blob.end(), koff.begin(), koff.end());
-    size_t o_kreq = blob.size();
-    blob.insert(blob.end(), kreq.begin(), kreq.end());
-    size_t o_nsv = blob.size();
-    blob.insert(blob.end(), nsv.begin(), nsv.end());
-    size_t o_nsoff = blob.size();
-    blob.insert(blob.end(), nsoff.begin(), nsoff.end());
-    size_t o_nsreq = blob.size();
-    blob.insert(blob.end(), nsreq.begin(), nsreq.end());
-    blob.push_back(0);
-    HIPC(B.tab.reserve(blob.size() + 2));
-    HIPC(hipMemcpyAsync(B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipStreamSynchronize(st));  // blob is pageable
-    const uint32_t* tb = B.tab.get();
-    const CandTab T{(const u64*)tb, tb + o_kall, tb + o_koff, tb + o_kreq, K, tb + o_nsv, tb + o_nsoff, tb + o_nsreq, M};
-    u64 ccap = std::max<u64>(65536, B.cq.cap()), dcap = M ? std::max<u64>(65536, B.dkeys.cap()) : 0;
-    for (;;) {
-      HIPC(B.cq.reserve((size_t)ccap));
-      HIPC(B.creq.reserve((size_t)ccap));
-      if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
-      HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, st));  // ccount, dcount
-      hipLaunchKernelGGL(k_lk_scan, dim3(std::max(1u, std::min(grid_wide, nn / 256 + 1))), dim3(256), 0, st, ds, T,
-                         (const kg_lookup*)B.d_req.get(), B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap,
-                         B.ctl.get());
-      HIPC(hipGetLastError());
-      LkCtl h;
-      if (int rc = read_ctl(w, B, st, &h)) return rc;
-      if (h.dcount > dcap) {
-        dcap = h.dcount;
-        ccap = std::max(ccap, h.ccount);
-        continue;
-      }
-      if (h.ccount <= ccap && h.dcount) {
-        const size_t nd = (size_t)h.dcount;
-        HIPC(B.dkeys2.reserve(nd));
-        hipcub::DoubleBuffer<u64> kb(B.dkeys.get(), B.dkeys2.get());
-        size_t sort_bytes = 0;
-        HIPC(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, nd, 0, 64, st));
-        HIPC(B.tmp.reserve(sort_bytes + 16));
-        HIPC(hipcub::DeviceRadixSort::SortKeys(B.tmp.get(), sort_bytes, kb, nd, 0, 64, st));
-        hipLaunchKernelGGL(k_lk_domain, dim3((uint32_t)std::min<u64>(grid_wide, nd / 256 + 1)), dim3(256), 0, st, T,
-                           (const u64*)kb.Current(), (u64)nd, (const kg_lookup*)B.d_req.get(), B.cq.get(),
-                           B.creq.get(), ccap, B.ctl.get());
-        HIPC(hipGetLastError());
-        if (int rc = read_ctl(w, B, st, &h)) return rc;
-      }
-      if (h.ccount > ccap) {
-        ccap = h.ccount;
-        continue;
-      }
-      n_cand = h.ccount;
-      break;
-    }
-  }
-  if (n_cand) {
-    HIPC(B.cout.reserve((size_t)n_cand));
-    HIPC(B.cerr.reserve((size_t)n_cand));
-    constexpr u64 CHUNK = 1ull << 28;
-    for (u64 at = 0; at < n_cand; at += CHUNK) {
-      const size_t m = (size_t)std::min(CHUNK, n_cand - at);
-      if (int rc = check_batch_device(s, w, B.cq.get() + at, m, gmax, B.cout.get() + at, B.cerr.get() + at, nullptr))
-        return rc;
-    }
-    if (int rc = collect<false>(s, w, B, st, n_cand, O, &n_conf)) return rc;
-  }
-  if (int rc = lk_output(s, w, B, st, n, O.have, out)) return rc;
-  out->exact = n_exact;
-  out->candidates = n_cand;
-  out->confirmed = n_conf;
-  out->reverse_edges = st_edges;
-  out->levels = st_levels;
+// keys a[0, n) sorted over their bits [0, end_bit): *out (in a or b); with n_uniq, one of each.
+template <class K>
+int sort_keys(Call& c, DevBuf<K>& a, DevBuf<K>& b, size_t n, int end_bit, const K** out, u64* n_uniq) {
+  LookupBufs& B = c.B;
+  HIPC(b.reserve(n));
+  hipcub::DoubleBuffer<K> kb(a.get(), b.get());
+  size_t sort_bytes = 0, uniq_bytes = 0;
+  HIPC(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, n, 0, end_bit, c.st));
+  if (n_uniq) HIPC(hipcub::DeviceSelect::Unique(nullptr, uniq_bytes, (K*)nullptr, (K*)nullptr, (u64*)nullptr, n, c.st));
+  HIPC(B.tmp.reserve(std::max(sort_bytes, uniq_bytes) + 16));
+  HIPC(hipcub::DeviceRadixSort::SortKeys(B.tmp.get(), sort_bytes, kb, n, 0, end_bit, c.st));
+  *out = kb.Current();
+  if (!n_uniq) return 0;
+  HIPC(hipcub::DeviceSelect::Unique(B.tmp.get(), uniq_bytes, kb.Current(), kb.Alternate(), &B.ctl.get()->nuniq, n, c.st));
+  LkCtl h;
+  if (int rc = c.read_ctl(&h)) return rc;
+  *n_uniq = std::min<u64>(h.nuniq, n);
+  *out = kb.Alternate();
   return 0;
 }
 
-namespace {
-
-int lk_output(Snapshot* s, Workspace* w, LookupBufs& B, hipStream_t st, size_t n, u64 o_have, kg_lookup_buf* out) {
-  const uint32_t grid_wide = (uint32_t)s->n_cu * 4;
+int Call::finish(kg_lookup_buf* out) {
   u64 m = 0;
   const u64* uk = B.okeys.get();
-  if (o_have) {
-    HIPC(B.okeys2.reserve((size_t)std::max<u64>(o_have, 1)));
-    hipcub::DoubleBuffer<u64> kb(B.okeys.get(), B.okeys2.get());
+  if (O.have) {
     int end_bit = 33;
     while (end_bit < 64 && ((u64)n >> (end_bit - 32))) end_bit++;
-    size_t sort_bytes = 0, uniq_bytes = 0;
-    HIPC(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, (size_t)o_have, 0, end_bit, st));
-    HIPC(hipcub::DeviceSelect::Unique(nullptr, uniq_bytes, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, (size_t)o_have, st));
-    HIPC(B.tmp.reserve(std::max(sort_bytes, uniq_bytes) + 16));
-    HIPC(hipcub::DeviceRadixSort::SortKeys(B.tmp.get(), sort_bytes, kb, (size_t)o_have, 0, end_bit, st));
-    HIPC(hipcub::DeviceSelect::Unique(B.tmp.get(), uniq_bytes, kb.Current(), kb.Alternate(), &B.ctl.get()->nuniq,
-                                      (size_t)o_have, st));
-    LkCtl h;
-    if (int rc = read_ctl(w, B, st, &h)) return rc;
-    m = std::min(h.nuniq, o_have);
-    uk = kb.Alternate();
+    if (int rc = sort_keys(*this, B.okeys, B.okeys2, (size_t)O.have, end_bit, &uk, &m)) return rc;
   }
   HIPC(B.d_off.reserve(n + 1));
   HIPC(B.d_objs.reserve((size_t)std::max<u64>(m, 1)));
@@ -1085,130 +742,354 @@ int lk_output(Snapshot* s, Workspace* w, LookupBufs& B, hipStream_t st, size_t n
   out->n_objs = m;
   out->kernel_ms = ms;
   out->pinned = bytes;
+  out->exact = n_exact;
+  out->candidates = n_cand;
+  out->confirmed = n_conf;
+  out->reverse_edges = st_edges;
+  out->levels = st_levels;
+  return 0;
+}
+
+// The candidates' answers join the output keys (k_lk_collect); errors are counted on the first pass only.
+template <bool SUBJ>
+int collect(Call& c, u64 n_cand) {
+  LookupBufs& B = c.B;
+  for (int pass = 0;; pass++) {
+    hipLaunchKernelGGL(k_lk_collect<SUBJ>, dim3((uint32_t)std::min<u64>(c.grid_wide, n_cand / 256 + 1)), dim3(256), 0,
+                       c.st, (const kg_query*)B.cq.get(), (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(),
+                       (const uint32_t*)B.cerr.get(), n_cand, B.okeys.get(), c.O.cap, pass == 0 ? 1 : 0,
+                       B.n_errors.get(), B.errmin.get(), B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    if (h.ocount > c.O.cap) {
+      if (pass) return set_error(KG_ERR_RESOURCE_CODE, "lookup: output list overflowed twice");
+      if (int rc = c.regrow_out(h.ocount)) return rc;
+      continue;
+    }
+    c.O.have = h.ocount;
+    c.n_conf = h.confirmed;
+    return 0;
+  }
+}
+
+// ------------------------------------------------------------------ host: the walk
+// The walk buffers of a lane: allocated for the snapshot's nodes on first use, the masks all clear on
+// return, the call's request bits on the device.  *scan_bytes: hipcub's scan temporaries.
+int walk_reserve(Call& c, const std::vector<GReq>& greq, size_t* scan_bytes) {
+  LookupBufs& B = c.B;
+  const uint32_t nn = c.s->ds.n_nodes;
+  if (B.walk_nodes < nn) {
+    B.walk_nodes = 0;
+    for (auto* b : {&B.vis, &B.next, &B.cmask}) HIPC(b->reserve(nn));
+    for (auto* b : {&B.len, &B.pref}) HIPC(b->reserve((size_t)nn + 1));
+    for (auto* b : {&B.fl[0], &B.fl[1], &B.touched}) HIPC(b->reserve(nn));
+    B.walk_nodes = nn;
+    B.dirty = true;
+  }
+  if (B.dirty) {
+    HIPC(hipMemsetAsync(B.vis.get(), 0, (size_t)B.walk_nodes * 8, c.st));
+    HIPC(hipMemsetAsync(B.next.get(), 0, (size_t)B.walk_nodes * 8, c.st));
+    B.dirty = false;
+  }
+  HIPC(B.greq.reserve(greq.size()));
+  HIPC(hipMemcpyAsync(B.greq.get(), greq.data(), greq.size() * sizeof(GReq), hipMemcpyHostToDevice, c.st));
+  HIPC(hipStreamSynchronize(c.st));  // greq is pageable
+  *scan_bytes = 0;
+  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, *scan_bytes, B.len.get(), B.pref.get(), (size_t)nn + 1, c.st));
+  HIPC(B.tmp.reserve(*scan_bytes + 16));
+  return 0;
+}
+
+// After a group: the masks cleared by replaying the touched list, the node lists empty.  h: the
+// counters as the group's last launch left them.
+int walk_finish(Call& c, const LkCtl& h) {
+  LookupBufs& B = c.B;
+  hipLaunchKernelGGL(k_lk_clear, dim3(c.grid_wide), dim3(256), 0, c.st, B.vis.get(), B.next.get(),
+                     (const uint32_t*)B.touched.get(), B.walk_nodes, B.ctl.get());
+  hipLaunchKernelGGL(k_lk_lists_reset, dim3(1), dim3(1), 0, c.st, B.ctl.get());
+  HIPC(hipGetLastError());
+  HIPC(hipStreamSynchronize(c.st));
+  B.dirty = h.over != 0;  // an overflowed touched list did not name every node to clear
+  if (h.over) return set_error(KG_ERR_RESOURCE_CODE, "lookup: a node list overflowed");
+  return 0;
+}
+
+// A frontier above PREFIX_IN_KERNEL entries: its row lengths (B.len) and their prefix (B.pref).
+template <class Len>
+int prep_large(Call& c, uint32_t F, Len len_of, uint32_t* fcount_out, size_t scan_bytes) {
+  hipLaunchKernelGGL(k_lk_prep<Len>, dim3(F / 256 + 1), dim3(256), 0, c.st, F, len_of, c.B.len.get(), fcount_out);
+  HIPC(hipcub::DeviceScan::ExclusiveSum(c.B.tmp.get(), scan_bytes, c.B.len.get(), c.B.pref.get(), (size_t)F + 1, c.st));
+  return 0;
+}
+
+// The level's first prepare: lengths len_a -> B.pref, resetting the list the level builds; a frontier of
+// up to PREFIX_IN_KERNEL entries in one launch, together with len_b -> B.len (the forward walk's adj rows).
+template <class LenA, class LenB>
+int prep_first(Call& c, const Walk& W, uint32_t F, LenA len_a, LenB len_b, size_t scan_bytes) {
+  uint32_t* fc_out = &c.B.ctl.get()->fcount[W.fsel];
+  if (F > PREFIX_IN_KERNEL) return prep_large(c, F, len_a, fc_out, scan_bytes);
+  hipLaunchKernelGGL((k_lk_prep_scan<LenA, LenB>), dim3(1), dim3(256), 0, c.st, F, len_a, c.B.pref.get(), len_b,
+                     c.B.len.get(), fc_out);
+  return 0;
+}
+
+template <class Body>
+void launch_edges(Call& c, const Frontier& f, const Rows& r, const u64* pref, const Body& body) {
+  hipLaunchKernelGGL(k_lk_frontier_edges<Body>, dim3(c.grid_wide), dim3(256), 0, c.st, f, r, pref, c.B.ctl.get(), body);
+}
+
+// The direction policies of walk_groups.  res: the resolved requests (.depth); seed(): the launch of
+// level 0 -- true: *F is its frontier's size, false: read it back; level(): the launches of level j >=
+// FIRST_LEVEL on the frontier f -- *expanded == false: they built no next frontier, the group's walk ends.
+//
+// Reverse: the seed lists the subject's holders; level j = 1 .. D-1 follows the frontier's reverse edges.
+struct ReverseWalk {
+  const LReq* res;
+  static constexpr int32_t FIRST_LEVEL = 1;
+  bool seed(Call& c, const Walk& W, const GReq*, uint32_t gn, uint32_t*) const {
+    hipLaunchKernelGGL(k_lk_seed, dim3(gn), dim3(256), 0, c.st, c.s->ds, W, (const LReq*)c.B.d_res.get());
+    return false;
+  }
+  int level(Call& c, const Walk& W, const Frontier& f, u64 live, u64, size_t scan_bytes, bool* expanded) const {
+    const DevSnap& ds = c.s->ds;
+    const RowLen<true> take{f, ds.radj_off, live, c.B.next.get(), ds.nflags};
+    if (int rc = prep_first(c, W, f.F, take, NoLen{}, scan_bytes)) return rc;
+    launch_edges(c, f, Rows{ds.radj_off, ds.radj, c.s->n_set_edges}, c.B.pref.get(), Hop<true>{ds, W, ~0ull});
+    *expanded = true;
+    return 0;
+  }
+};
+
+// Forward: level j = 0 .. D-1 lists the subject ids of the frontier's check rows (emit) and, for the
+// requests that go one level further (xlive), follows its adj rows (expand).
+struct ForwardWalk {
+  const SReq* res;
+  Rows check;  // the check rows
+  static constexpr int32_t FIRST_LEVEL = 0;
+  // the first frontier is the group's distinct roots: no readback before level 0
+  bool seed(Call& c, const Walk& W, const GReq* g, uint32_t gn, uint32_t* F) const {
+    hipLaunchKernelGGL(k_ls_seed, dim3(1), dim3(64), 0, c.st, c.s->ds, W, gn);
+    std::set<uint32_t> roots;
+    for (uint32_t b = 0; b < gn; b++) roots.insert(g[b].root);
+    *F = (uint32_t)roots.size();
+    return true;
+  }
+  int level(Call& c, const Walk& W, const Frontier& f, u64 live, u64 xlive, size_t scan_bytes, bool* expanded) const {
+    const DevSnap& ds = c.s->ds;
+    const RowLen<true> take{f, check.off, live, c.B.next.get(), nullptr};
+    const RowLen<false> kept{f, ds.adj_off, xlive, nullptr, nullptr};
+    if (int rc = prep_first(c, W, f.F, take, kept, scan_bytes)) return rc;
+    launch_edges(c, f, check, c.B.pref.get(), EmitIds{W});
+    *expanded = xlive != 0;
+    if (!xlive) return 0;
+    const u64* apref = c.B.len.get();  // the prefix of the adj rows
+    if (f.F > PREFIX_IN_KERNEL) {  // the emit has read pref: the same two buffers take the adj rows
+      if (int rc = prep_large(c, f.F, kept, (uint32_t*)nullptr, scan_bytes)) return rc;
+      apref = c.B.pref.get();
+    }
+    launch_edges(c, f, Rows{ds.adj_off, ds.adj, c.s->n_set_edges}, apref, Hop<false>{ds, W, xlive});
+    return 0;
+  }
+};
+
+// The walk of a call, 64 requests per group.  The counters are read back after every level that built a
+// frontier, and once more at the end if the last one did not.
+template <class Dir>
+int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
+  if (greq.empty()) return 0;
+  LookupBufs& B = c.B;
+  size_t scan_bytes = 0;
+  if (int rc = walk_reserve(c, greq, &scan_bytes)) return rc;
+  for (size_t g0 = 0; g0 < greq.size();) {
+    const uint32_t gn = (uint32_t)std::min<size_t>(64, greq.size() - g0);
+    int32_t max_d = 1;
+    for (uint32_t b = 0; b < gn; b++) max_d = std::max(max_d, dir.res[greq[g0 + b].req].depth);
+    Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), c.O.cap,
+           B.greq.get() + g0, B.ctl.get()};
+    B.dirty = true;
+    LkCtl h;
+    uint32_t cur = 0, F = 0;
+    bool h_now = !dir.seed(c, W, &greq[g0], gn, &F);  // h holds the counters as they are on the device
+    HIPC(hipGetLastError());
+    if (h_now) {
+      if (int rc = c.read_ctl(&h)) return rc;
+      F = std::min(h.fcount[0], B.walk_nodes);
+    }
+    for (int32_t j = Dir::FIRST_LEVEL; j <= max_d - 1 && F; j++) {
+      u64 live = 0, xlive = 0;  // requests whose depth reaches level j / goes on into level j + 1
+      for (uint32_t b = 0; b < gn; b++) {
+        const int32_t d = dir.res[greq[g0 + b].req].depth;
+        if (d - 1 >= j) live |= 1ull << b;
+        if (d - 1 >= j + 1) xlive |= 1ull << b;
+      }
+      W.fout = B.fl[cur ^ 1].get();
+      W.fsel = cur ^ 1;
+      bool expanded = false;
+      h_now = false;
+      const Frontier f{B.fl[cur].get(), B.cmask.get(), F};
+      if (int rc = dir.level(c, W, f, live, xlive, scan_bytes, &expanded)) return rc;
+      HIPC(hipGetLastError());
+      c.st_levels++;
+      if (!expanded) break;
+      if (int rc = c.read_ctl(&h)) return rc;
+      h_now = true;
+      cur ^= 1;
+      F = std::min(h.fcount[cur], B.walk_nodes);
+    }
+    if (!h_now)
+      if (int rc = c.read_ctl(&h)) return rc;
+    if (int rc = walk_finish(c, h)) return rc;
+    if (h.ocount > c.O.cap) {  // the group's keys did not fit: a larger list, the group again
+      if (int rc = c.regrow_out(h.ocount)) return rc;
+      continue;
+    }
+    c.O.have = h.ocount;
+    c.st_edges = h.edges;  // summed on the device over every run, reruns included
+    g0 += gn;
+  }
+  c.n_exact = c.O.have;
   return 0;
 }
 
 }  // namespace
 
+void lookup_bufs_free(void* p) { delete static_cast<LookupBufs*>(p); }
+
+// kg_lookup_objects on lane L (its stream and workspace; the caller holds the workspace's mutex).
+int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+  Call c(s, L, gmax);
+  LookupBufs& B = c.B;
+  hipStream_t st = c.st;
+  const DevSnap& ds = s->ds;
+  const LReq* lr = nullptr;
+  if (int rc = c.begin(reqs, n, &lr, [&](uint32_t blocks, const kg_lookup* d_req, LReq* d_lr) {
+        hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, st, ds, d_req, (uint32_t)n, c.gmax,
+                           (uint64_t)s->n_check_rows, d_lr);
+      }))
+    return rc;
+
+  // ---- plan: walk groups and candidate tables
+  std::vector<GReq> greq;
+  std::map<u64, std::vector<uint32_t>> by_key;
+  std::map<uint32_t, std::vector<uint32_t>> by_ns;
+  for (size_t i = 0; i < n; i++) {
+    if (lr[i].mode == LK_ALL) {
+      by_ns[reqs[i].ns].push_back((uint32_t)i);
+      continue;
+    }
+    if (lr[i].mode == LK_REVERSE && lr[i].hcount) greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0});
+    // candidates of a reverse request: impure nodes -- none without node flags
+    if (lr[i].mode == LK_NODES || ds.nflags) by_key[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
+  }
+  if (int rc = walk_groups(c, greq, ReverseWalk{lr})) return rc;
+
+  // ---- candidates: one pass over the nodes, then the sorted domains of the confirm-all namespaces
+  if (!by_key.empty() || !by_ns.empty()) {
+    std::vector<uint32_t> blob;
+    const uint32_t K = (uint32_t)by_key.size(), M = (uint32_t)by_ns.size();
+    // layout (u32 words): keys[2K] | kall[K] | koff[K+1] | kreq[..] | nsv[M] | nsoff[M+1] | nsreq[..]
+    std::vector<u64> keys;
+    std::vector<uint32_t> kall, koff{0}, kreq, nsv, nsoff{0}, nsreq;
+    for (auto& kv : by_key) {
+      keys.push_back(kv.first);
+      kall.push_back(lr[kv.second[0]].mode == LK_NODES ? 1u : 0u);
+      kreq.insert(kreq.end(), kv.second.begin(), kv.second.end());
+      koff.push_back((uint32_t)kreq.size());
+    }
+    for (auto& kv : by_ns) {
+      nsv.push_back(kv.first);
+      nsreq.insert(nsreq.end(), kv.second.begin(), kv.second.end());
+      nsoff.push_back((uint32_t)nsreq.size());
+    }
+    blob.resize(2 * (size_t)K);
+    if (K) memcpy(blob.data(), keys.data(), (size_t)K * 8);
+    auto put = [&blob](const std::vector<uint32_t>& v) {
+      blob.insert(blob.end(), v.begin(), v.end());
+      return blob.size() - v.size();
+    };
+    const size_t o_kall = put(kall), o_koff = put(koff), o_kreq = put(kreq), o_nsv = put(nsv), o_nsoff = put(nsoff),
+                 o_nsreq = put(nsreq);
+    blob.push_back(0);
+    HIPC(B.tab.reserve(blob.size() + 2));
+    HIPC(hipMemcpyAsync(B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st));
+    HIPC(hipStreamSynchronize(st));  // blob is pageable
+    const uint32_t* tb = B.tab.get();
+    const CandTab T{(const u64*)tb, tb + o_kall, tb + o_koff, tb + o_kreq, K, tb + o_nsv, tb + o_nsoff, tb + o_nsreq, M};
+    const kg_lookup* d_req = (const kg_lookup*)B.d_req.get();
+    u64 ccap = std::max<u64>(65536, B.cq.cap()), dcap = M ? std::max<u64>(65536, B.dkeys.cap()) : 0;
+    for (;;) {
+      HIPC(B.cq.reserve((size_t)ccap));
+      HIPC(B.creq.reserve((size_t)ccap));
+      if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
+      HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, st));  // ccount, dcount
+      hipLaunchKernelGGL(k_lk_scan, dim3(std::max(1u, std::min(c.grid_wide, ds.n_nodes / 256 + 1))), dim3(256), 0, st, ds,
+                         T, d_req, B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap, B.ctl.get());
+      HIPC(hipGetLastError());
+      LkCtl h;
+      if (int rc = c.read_ctl(&h)) return rc;
+      if (h.dcount > dcap) {
+        dcap = h.dcount;
+        ccap = std::max(ccap, h.ccount);
+        continue;
+      }
+      if (h.ccount <= ccap && h.dcount) {
+        const size_t nd = (size_t)h.dcount;
+        const u64* dk = nullptr;
+        if (int rc = sort_keys(c, B.dkeys, B.dkeys2, nd, 64, &dk, (u64*)nullptr)) return rc;
+        hipLaunchKernelGGL(k_lk_domain, dim3((uint32_t)std::min<u64>(c.grid_wide, nd / 256 + 1)), dim3(256), 0, st, T,
+                           dk, (u64)nd, d_req, B.cq.get(), B.creq.get(), ccap, B.ctl.get());
+        HIPC(hipGetLastError());
+        if (int rc = c.read_ctl(&h)) return rc;
+      }
+      if (h.ccount > ccap) {
+        ccap = h.ccount;
+        continue;
+      }
+      c.n_cand = h.ccount;
+      break;
+    }
+  }
+  if (c.n_cand) {
+    HIPC(B.cout.reserve((size_t)c.n_cand));
+    HIPC(B.cerr.reserve((size_t)c.n_cand));
+    constexpr u64 CHUNK = 1ull << 28;
+    for (u64 at = 0; at < c.n_cand; at += CHUNK) {
+      const size_t m = (size_t)std::min(CHUNK, c.n_cand - at);
+      if (int rc = check_batch_device(s, c.w, B.cq.get() + at, m, c.gmax, B.cout.get() + at, B.cerr.get() + at, nullptr))
+        return rc;
+    }
+    if (int rc = collect<false>(c, c.n_cand)) return rc;
+  }
+  return c.finish(out);
+}
+
 // kg_lookup_subjects on lane L (as lookup_objects).  Walk-mode requests are listed by the forward walk,
 // 64 per group; the others by a check of every subject id of the domain, in chunks of CHUNK pairs.
 int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
-  if (gmax < 1) gmax = 5;  // as check_batch_begin
-  if (n > 0x7FFFFFFFull) return set_error(-2, "batch too large");
-  HIPC(hipSetDevice(s->device));
-  hipStream_t st = L->stream;
-  Workspace* w = L->w;
-  if (!L->lk) L->lk = new LookupBufs();
-  LookupBufs& B = *static_cast<LookupBufs*>(L->lk);
+  Call c(s, L, gmax);
+  LookupBufs& B = c.B;
+  hipStream_t st = c.st;
   const DevSnap& ds = s->ds;
-  const uint32_t nn = ds.n_nodes;
-  const uint32_t grid_wide = (uint32_t)s->n_cu * 4;
-  const uint64_t* coff = ds.crow_off ? ds.crow_off : ds.row_off;
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
   const uint64_t n_rows = s->n_check_rows;
-  HIPC(B.h_sreq.reserve(n));
-  HIPC(B.d_sreq.reserve(n));
-  HIPC(B.d_sr.reserve(n));
-  HIPC(B.h_sr.reserve(n));
-  memcpy(B.h_sreq.get(), reqs, n * sizeof(kg_lookup_subj));
-  if (int rc = lk_begin(B, n, st)) return rc;
-  HIPC(hipMemcpyAsync(B.d_sreq.get(), B.h_sreq.get(), n * sizeof(kg_lookup_subj), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(k_ls_resolve, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, ds,
-                     (const kg_lookup_subj*)B.d_sreq.get(), (uint32_t)n, gmax, B.d_sr.get());
-  HIPC(hipGetLastError());
-  HIPC(hipMemcpyAsync(B.h_sr.get(), B.d_sr.get(), n * sizeof(SReq), hipMemcpyDeviceToHost, st));
-  if (int rc = w->wait(st, true)) return rc;
-  const SReq* sr = B.h_sr.get();
+  const SReq* sr = nullptr;
+  if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj* d_req, SReq* d_sr) {
+        hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, st, ds, d_req, (uint32_t)n, c.gmax, d_sr);
+      }))
+    return rc;
 
   std::vector<GReq> greq;      // walk mode, by group and bit
   std::vector<uint32_t> conf;  // confirm mode
   for (size_t i = 0; i < n; i++) {
-    if (sr[i].mode == LS_WALK && sr[i].root < nn) greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root});
+    if (sr[i].mode == LS_WALK && sr[i].root < ds.n_nodes)
+      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root});
     else if (sr[i].mode == LS_CONFIRM) conf.push_back((uint32_t)i);
   }
-
-  OutKeys O{B, w, st};
-  if (int rc = O.init(s)) return rc;
-  uint64_t st_edges = 0, st_levels = 0;
-
-  // ---- the forward walk
-  if (!greq.empty()) {
-    size_t scan_bytes = 0;
-    if (int rc = walk_reserve(B, nn, greq, st, &scan_bytes)) return rc;
-    for (size_t g0 = 0; g0 < greq.size();) {
-      const uint32_t gn = (uint32_t)std::min<size_t>(64, greq.size() - g0);
-      int32_t max_d = 1;
-      std::vector<uint32_t> roots;
-      for (uint32_t b = 0; b < gn; b++) {
-        max_d = std::max(max_d, sr[greq[g0 + b].req].depth);
-        roots.push_back(greq[g0 + b].root);
-      }
-      std::sort(roots.begin(), roots.end());
-      Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), O.cap,
-             B.greq.get() + g0, B.ctl.get()};
-      B.dirty = true;
-      hipLaunchKernelGGL(k_ls_seed, dim3(1), dim3(64), 0, st, ds, W, gn);
-      HIPC(hipGetLastError());
-      // the first frontier is the group's distinct roots: no readback before level 0
-      uint32_t cur = 0, F = (uint32_t)(std::unique(roots.begin(), roots.end()) - roots.begin());
-      LkCtl h;
-      bool h_now = false;  // h holds the counters as they are on the device
-      for (int32_t j = 0; j <= max_d - 1 && F; j++) {
-        h_now = false;
-        u64 live = 0, xlive = 0;  // requests that probe level j / expand it into level j + 1
-        for (uint32_t b = 0; b < gn; b++) {
-          const int32_t d = sr[greq[g0 + b].req].depth;
-          if (d - 1 >= j) live |= 1ull << b;
-          if (d - 1 >= j + 1) xlive |= 1ull << b;
-        }
-        W.fout = B.fl[cur ^ 1].get();
-        W.fsel = cur ^ 1;
-        uint32_t* fc_out = &B.ctl.get()->fcount[cur ^ 1];
-        const uint32_t* fl = B.fl[cur].get();
-        const u64* apref = B.pref.get();  // the prefix of the adj rows
-        if (F <= 4096) {
-          hipLaunchKernelGGL(k_ls_prep_scan, dim3(1), dim3(256), 0, st, ds, coff, B.next.get(), fl, F, live, xlive,
-                             B.cmask.get(), B.pref.get(), B.len.get(), fc_out);
-          apref = B.len.get();
-        } else {
-          hipLaunchKernelGGL(k_ls_prep, dim3(F / 256 + 1), dim3(256), 0, st, coff, B.next.get(), fl, F, live,
-                             B.cmask.get(), B.len.get(), fc_out);
-          HIPC(hipcub::DeviceScan::ExclusiveSum(B.tmp.get(), scan_bytes, B.len.get(), B.pref.get(), (size_t)F + 1, st));
-        }
-        hipLaunchKernelGGL(k_ls_emit, dim3(grid_wide), dim3(256), 0, st, W, coff, csub, fl, (const u64*)B.cmask.get(),
-                           (const u64*)B.pref.get(), F, n_rows);
-        HIPC(hipGetLastError());
-        st_levels++;
-        if (!xlive) break;
-        if (F > 4096) {  // the emit has read pref: the same two buffers take the adj rows
-          hipLaunchKernelGGL(k_ls_prep_adj, dim3(F / 256 + 1), dim3(256), 0, st, ds, fl, F, xlive,
-                             (const u64*)B.cmask.get(), B.len.get());
-          HIPC(hipcub::DeviceScan::ExclusiveSum(B.tmp.get(), scan_bytes, B.len.get(), B.pref.get(), (size_t)F + 1, st));
-        }
-        hipLaunchKernelGGL(k_ls_expand, dim3(grid_wide), dim3(256), 0, st, ds, W, fl, (const u64*)B.cmask.get(), apref, F,
-                           xlive, (uint64_t)s->n_set_edges);
-        HIPC(hipGetLastError());
-        if (int rc = read_ctl(w, B, st, &h)) return rc;
-        h_now = true;
-        cur ^= 1;
-        F = std::min(h.fcount[cur], B.walk_nodes);
-      }
-      if (!h_now)
-        if (int rc = read_ctl(w, B, st, &h)) return rc;
-      if (int rc = walk_finish(s, B, st, h)) return rc;
-      if (h.ocount > O.cap) {  // the group's keys did not fit: a larger list, the group again
-        if (int rc = O.regrow(h.ocount)) return rc;
-        continue;
-      }
-      O.have = h.ocount;
-      st_edges = h.edges;  // summed on the device over every run, reruns included
-      g0 += gn;
-    }
-  }
-  const u64 n_exact = O.have;
+  if (int rc = walk_groups(c, greq, ForwardWalk{sr, Rows{ds.crow_off ? ds.crow_off : ds.row_off, csub, n_rows}})) return rc;
 
   // ---- confirmation: the domain once, then every (subject id, request) pair through the check
-  u64 n_cand = 0, n_conf = 0, n_dom = 0;
+  u64 n_dom = 0;
   const uint32_t* dom = nullptr;
   if (!conf.empty() && n_rows && csub) {
     const bool bits = ds.hbits && !s->lookup_domain_rows;
@@ -1217,14 +1098,14 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
       HIPC(B.dom.reserve((size_t)dcap));
       HIPC(hipMemsetAsync(&B.ctl.get()->dcount, 0, 8, st));
       if (bits)
-        hipLaunchKernelGGL(k_ls_dom_bits, dim3(std::min(grid_wide, ds.hbits_n / 8192 + 1)), dim3(256), 0, st, ds.hbits,
+        hipLaunchKernelGGL(k_ls_dom_bits, dim3(std::min(c.grid_wide, ds.hbits_n / 8192 + 1)), dim3(256), 0, st, ds.hbits,
                            ds.hbits_n, B.dom.get(), dcap, B.ctl.get());
       else
-        hipLaunchKernelGGL(k_ls_dom_rows, dim3((uint32_t)std::min<u64>(grid_wide, n_rows / 256 + 1)), dim3(256), 0, st,
+        hipLaunchKernelGGL(k_ls_dom_rows, dim3((uint32_t)std::min<u64>(c.grid_wide, n_rows / 256 + 1)), dim3(256), 0, st,
                            csub, (u64)n_rows, B.dom.get(), dcap, B.ctl.get());
       HIPC(hipGetLastError());
       LkCtl h;
-      if (int rc = read_ctl(w, B, st, &h)) return rc;
+      if (int rc = c.read_ctl(&h)) return rc;
       if (h.dcount > dcap) {
         dcap = h.dcount;
         continue;
@@ -1233,52 +1114,32 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
       break;
     }
     dom = B.dom.get();
-    if (!bits && n_dom) {  // an id per row entry that holds it: sort, one of each
-      HIPC(B.dom2.reserve((size_t)n_dom));
-      hipcub::DoubleBuffer<uint32_t> kb(B.dom.get(), B.dom2.get());
-      size_t sort_bytes = 0, uniq_bytes = 0;
-      HIPC(hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, kb, (size_t)n_dom, 0, 31, st));
-      HIPC(hipcub::DeviceSelect::Unique(nullptr, uniq_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (u64*)nullptr,
-                                        (size_t)n_dom, st));
-      HIPC(B.tmp.reserve(std::max(sort_bytes, uniq_bytes) + 16));
-      HIPC(hipcub::DeviceRadixSort::SortKeys(B.tmp.get(), sort_bytes, kb, (size_t)n_dom, 0, 31, st));
-      HIPC(hipcub::DeviceSelect::Unique(B.tmp.get(), uniq_bytes, kb.Current(), kb.Alternate(), &B.ctl.get()->nuniq,
-                                        (size_t)n_dom, st));
-      LkCtl h;
-      if (int rc = read_ctl(w, B, st, &h)) return rc;
-      n_dom = std::min(h.nuniq, n_dom);
-      dom = kb.Alternate();
-    }
+    if (!bits && n_dom)  // an id per row entry that holds it: sort, one of each
+      if (int rc = sort_keys(c, B.dom, B.dom2, (size_t)n_dom, 31, &dom, &n_dom)) return rc;
   }
   if (n_dom) {
     const uint32_t C = (uint32_t)conf.size();
     HIPC(B.tab.reserve(C));
     HIPC(hipMemcpyAsync(B.tab.get(), conf.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
     HIPC(hipStreamSynchronize(st));  // conf is pageable
-    n_cand = n_dom * C;
+    c.n_cand = n_dom * C;
     constexpr u64 CHUNK = 1ull << 22;
-    const size_t ccap = (size_t)std::min(CHUNK, n_cand);
+    const size_t ccap = (size_t)std::min(CHUNK, c.n_cand);
     HIPC(B.cq.reserve(ccap));
     HIPC(B.creq.reserve(ccap));
     HIPC(B.cout.reserve(ccap));
     HIPC(B.cerr.reserve(ccap));
-    for (u64 at = 0; at < n_cand; at += CHUNK) {
-      const u64 m = std::min(CHUNK, n_cand - at);
-      hipLaunchKernelGGL(k_ls_cands, dim3((uint32_t)std::min<u64>(grid_wide, m / 256 + 1)), dim3(256), 0, st, dom, n_dom,
-                         (const uint32_t*)B.tab.get(), C, (const kg_lookup_subj*)B.d_sreq.get(), at, m, B.cq.get(),
+    for (u64 at = 0; at < c.n_cand; at += CHUNK) {
+      const u64 m = std::min(CHUNK, c.n_cand - at);
+      hipLaunchKernelGGL(k_ls_cands, dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)), dim3(256), 0, st, dom, n_dom,
+                         (const uint32_t*)B.tab.get(), C, (const kg_lookup_subj*)B.d_req.get(), at, m, B.cq.get(),
                          B.creq.get());
       HIPC(hipGetLastError());
-      if (int rc = check_batch_device(s, w, B.cq.get(), (size_t)m, gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;
-      if (int rc = collect<true>(s, w, B, st, m, O, &n_conf)) return rc;
+      if (int rc = check_batch_device(s, c.w, B.cq.get(), (size_t)m, c.gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;
+      if (int rc = collect<true>(c, m)) return rc;
     }
   }
-  if (int rc = lk_output(s, w, B, st, n, O.have, out)) return rc;
-  out->exact = n_exact;
-  out->candidates = n_cand;
-  out->confirmed = n_conf;
-  out->reverse_edges = st_edges;
-  out->levels = st_levels;
-  return 0;
+  return c.finish(out);
 }
 
 void lookup_free(kg_lookup_buf* out) {

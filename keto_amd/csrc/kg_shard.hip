@@ -286,8 +286,7 @@ __device__ __forceinline__ SeedQ seed_query(const DevSnap& s, const kg_query* __
     const uint32_t sn = nmap_find(s, x.t.sns, x.t.srel, x.t.sobj);
     subj = sn == NONE ? NONE : (SET_BIT | sn);
   }
-  int32_t d = x.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:68-70
+  const int32_t d = clamp_depth(x.max_depth, global);
   res[i] = KG_NOT_MEMBER;
   err[i] = KG_ERR_NONE;
   const uint8_t rf = relflag(s, x.t.ns, x.t.rel);
@@ -1039,7 +1038,7 @@ __global__ void k_shard_bad_nodes(DevSnap s, unsigned long long* count) {
   if (bad && s.radj_off) {
     const bool reached = s.radj_off[v + 1] > s.radj_off[v];
     const uint32_t ns = s.nd_ns[v], rel = s.nd_rel[v];
-    const bool vunion = s.virt && ns < s.n_ns && rel < s.n_rel && s.virt[(size_t)ns * s.n_rel + rel];
+    const bool vunion = rel_is_union(s, ns, rel);
     const bool owned = !s.nowner || s.nowner[v] == s.shard_rank;
     bad = reached || (vunion && owned && s.shard_n > 1);
   }

@@ -357,8 +357,7 @@ extern "C" int kg_check_tree(kg_snapshot* sp, const kg_query* q, int32_t global_
     *result = r;
     if (err_code) *err_code = e;
     if (r != KG_IS_MEMBER) return 0;  // only a member has a tree (engine.go:65-80)
-    int32_t d = q->max_depth;
-    if (d <= 0 || global_max_depth < d) d = global_max_depth;  // engine.go:68-70
+    const int32_t d = kg::clamp_depth(q->max_depth, global_max_depth);
     kg::Explain x(s, sp, global_max_depth, hidden_rels, n_hidden);
     const kg::Q6 root{q->t.ns, q->t.obj, q->t.rel, q->t.sns, q->t.sobj, q->t.srel};
     const int t = x.tree(root, d);
