@@ -201,6 +201,20 @@ __global__ void k_delta_adjoff(const uint64_t* __restrict__ row_off, uint32_t n,
   if (v <= n) adj_off[v] = pos[row_off[v]];  // pos has n_rows + 1 entries (exclusive scan + total)
 }
 
+// Live nodes (DevSnap::nlive): a non-empty raw row, or named by a subject set of a raw row ("..." ones
+// included: they are in the rows, not in adj).  live[] starts at 0 and both kernels only ever store 1.
+__global__ void k_delta_live_rows(const uint64_t* __restrict__ row_off, uint32_t n, uint8_t* __restrict__ live) {
+  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v < n && row_off[v + 1] > row_off[v]) live[v] = 1;
+}
+__global__ void k_delta_live_sets(const uint32_t* __restrict__ row_subj, uint64_t n_rows, uint32_t n,
+                                  uint8_t* __restrict__ live) {
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n_rows; i += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t s = row_subj[i];
+    if ((s & SET_BIT) && (s & ~SET_BIT) < n) live[s & ~SET_BIT] = 1;
+  }
+}
+
 int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint64_t* ins_keys, size_t n_ins,
                                 const kg_tuple* del, size_t n_del, const kg_dict* dict, const kg_rewrite_prog* prog) {
   if (base->shard_n > 1) return set_error(-2, "kg_snapshot_apply: sharded snapshots rebuild instead");
@@ -450,6 +464,20 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   if (has_program && device_flags()) return -1;
   n_check_rows = h_row_off_last;
   if (augment_rewrites() || build_formulas()) return -1;
+  // 7. which nodes still make their object occur (the raw rows: materialisation leaves them as they are
+  // and gives its new nodes empty ones)
+  if (ds.n_nodes) {
+    uint8_t* live;
+    if (alloc((void**)&live, (size_t)ds.n_nodes + 16)) return -1;
+    HIPC(hipMemsetAsync(live, 0, (size_t)ds.n_nodes + 16, stream));
+    hipLaunchKernelGGL(k_delta_live_rows, dim3((ds.n_nodes + 255) / 256), dim3(256), 0, stream, ds.row_off, ds.n_nodes,
+                       live);
+    if (total)
+      hipLaunchKernelGGL(k_delta_live_sets, dim3((uint32_t)std::min<uint64_t>(2048, (total + 255) / 256)), dim3(256), 0,
+                         stream, ds.row_subj, total, ds.n_nodes, live);
+    HIPC(hipGetLastError());
+    ds.nlive = live;
+  }
   return build_hash_tables();
 }
 

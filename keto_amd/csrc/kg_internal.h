@@ -21,6 +21,8 @@
 //   hold[] u32 + subject hash             holders: the nodes whose row contains a given subject,
 //   hbits[] u32                           holder bitmap over subject ids (k_resolve's no-holder test)
 //                                        grouped by subject (the backward tier's level 0).
+//   nlive[n_nodes] u8                     refreshed snapshots only: the node still occurs in a tuple
+//                                        (kg_lookup_objects' domain); nullptr: every node does.
 #pragma once
 #include <stdint.h>
 
@@ -224,6 +226,11 @@ struct DevSnap {
   // row -- what nmap slots and adjx records carry; adj_off still gives lengths and the adj rows.
   // nullptr: adjx is parallel to adj (begin = adj_off)
   const uint32_t* adjx_off;
+  // refreshed snapshots (kg_delta.hip): [n_nodes] 1 = the node's raw row is non-empty or a raw row's
+  // subject set names it.  A refresh never drops a node id, so a node whose last tuple was deleted stays
+  // behind with an empty row; it no longer makes its object occur in the snapshot (kg_lookup_objects'
+  // domain).  nullptr: every node is live (a full build creates nodes from its tuples only)
+  const uint8_t* nlive;
 };
 constexpr uint32_t ADJX_REMOTE = 0x80000000u;
 

@@ -468,7 +468,8 @@ __device__ __forceinline__ void lk_emit_cands(uint32_t c, const uint32_t* reqs, 
 }
 
 // One pass over the nodes: the candidate nodes of the reverse / confirm-nodes requests become checks,
-// the objects of the confirm-all requests' namespaces become domain keys (sorted and deduplicated next).
+// the objects of the confirm-all requests' namespaces become domain keys (sorted and deduplicated next);
+// on a refreshed snapshot only live nodes give one (DevSnap::nlive).
 __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_lookup* __restrict__ q, kg_query* cq,
                                                  uint32_t* creq, u64 ccap, u64* dkeys, u64 dcap, LkCtl* ctl) {
   const uint32_t stride = gridDim.x * 256;
@@ -482,7 +483,8 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
         k = lk_find(T.keys, T.K, ((u64)ns << 32) | rel);
         if (k != NONE && (T.kall[k] || (s.nflags && (s.nflags[v] & NF_IMPURE)))) c = T.koff[k + 1] - T.koff[k];
       }
-      if (T.M) slot = lk_find(T.nsv, T.M, ns);
+      // the domain: objects that occur in a tuple -- not the node a refresh left behind without one
+      if (T.M && (!s.nlive || s.nlive[v])) slot = lk_find(T.nsv, T.M, ns);
     }
     lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
     lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
