@@ -274,10 +274,12 @@ int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
  * newly reached node instead of marking its holders in the group's target masks.  key "grid_ms_cap": entries per MS-BFS level buffer (0 = 16 Mi; small values force the
  * overflow reruns in tests).
  * key "grid_bidir" (0..2^31-1, default 0): grid-tier slots whose subject has at most this many
- * holders alternate forward and backward turns (0: forward only).  key "expand_tail" (0/1, default
- * 1): the expand walk caches a root's last frontier in LDS.  key "expand_gw" (0/1, default 1): roots
- * that outgrow the LDS pass gather their neighbourhood in parallel and walk the copy (small and large
- * workgroup slots, then the hash pass); "expand_skip_lds" (0/1, tests): every root skips the LDS pass.
+ * holders alternate forward and backward turns (0: forward only).  key "expand_gw" (0/1, default 1): roots
+ * that outgrow the LDS passes gather their neighbourhood in parallel and walk the copy (small and large
+ * workgroup slots, then the hash pass); "expand_skip_lds" (0/1/2, tests): 1 = every root skips the LDS
+ * passes, 2 = the 16-lane walkers are skipped and the 64-lane LDS pass takes every root;
+ * "expand_hash_cap" (4..2^18, default 2^18, tests): visited sets per hash-pass slot (small values send
+ * roots on to the whole-graph bitmap pass).
  * Hash-sharded mode: key "shard_wgs"
  * (1..64, default 8) k_shard_level workgroups per CU; "shard_heavy" (default 64) set rows longer than
  * this go to k_shard_heavy, which spreads their edges over the grid (0: every row); "shard_vis_mode"

@@ -505,6 +505,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     (strcmp(key, "expand_gw") == 0 ? s->expand_gw : s->expand_skip_lds) = (int)value;
     return 0;
   }
+  if (strcmp(key, "expand_hash_cap") == 0) {
+    if (value < 4 || value > (1 << 18)) return set_error(-2, "expand_hash_cap must be in [4, 2^18]");
+    s->expand_hash_cap = (uint32_t)value;
+    return 0;
+  }
   if (strcmp(key, "level_events") == 0) {
     if (value < 0 || value > 1) return set_error(-2, "level_events must be 0 or 1");
     s->level_events = (int)value;

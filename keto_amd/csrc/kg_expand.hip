@@ -7,13 +7,22 @@
 // (engine.go:37-39) is re-applied per level but is the identity below the root (children get
 // d-1 >= 1).
 //
-// One wave64 per root.  Every row subject yields exactly one child record, so a Union's child
+// One lane group per root.  Every row subject yields exactly one child record, so a Union's child
 // count (its row length) is known when it is emitted and the output is a single pre-order stream.
 // Order only matters for subject sets that will be EXPANDED (unvisited, rows non-empty, d-1 >= 2):
-// everything before the first such candidate in a 64-wide row chunk is emitted in parallel as
-// leaves, candidates are visited strictly in row order.  Output streams go to 1024-record chunks
-// of an HBM arena (bump allocator), then a compaction kernel lays each root out contiguously.
-// Visited sets live in LDS (pass 1); roots that outgrow LDS rerun with an HBM bitmap (pass 2).
+// everything before the first such candidate in a group-wide row chunk is emitted in parallel as
+// leaves, candidates are visited strictly in row order.  Output streams go to CHUNK-record (256)
+// chunks of an HBM arena (bump allocator), then a compaction kernel lays each root out contiguously.
+//
+// A root moves on to the next pass when it outgrows the visited store of the one it is in:
+//   pass 0  k_expand_sub   16 lanes a root, four roots a wave, LDS hash of SW_CAP sets, SW_RECS records
+//   pass 1  k_expand_lds   64 lanes a root, LDS hash + list of LIST sets
+//   pass 2  k_expand_gw    a workgroup gathers the root's neighbourhood, one wave walks the copy
+//                          (small slots, then large ones; skipped with expand_gw = 0)
+//           k_expand_hash  64 lanes a root, HBM hash + list of expand_hash_cap sets
+//   pass 3  k_expand_hbm   one slot, HBM bitmap over the whole graph
+// Passes 0, 1, the hash pass and pass 3 are ONE walk, expand_walk<G, Policy>: the policy says how a chunk
+// is fetched, how a set is marked visited and where frames live.  k_expand_gw has a walk of its own.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -22,6 +31,7 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "kg_bfs.h"
@@ -75,19 +85,59 @@ __device__ __forceinline__ unsigned long long ld_sc1(const unsigned long long* p
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// A free arena chunk (lane 0 only): from the range of this workgroup's XCD label, then the others;
-// NONE when all eight are used up.
-__device__ __forceinline__ uint32_t claim_chunk(ExpCtl* ctl, uint32_t n_chunks) {
-  const uint32_t per = (n_chunks + 7) / 8;
-  uint32_t sh = blockIdx.x & 7;
-  for (int k = 0; k < 8; k++, sh = (sh + 1) & 7) {
-    const uint32_t lo = sh * per, hi = min(n_chunks, lo + per);
-    if (lo >= hi) continue;
-    if (ld_sc1(&ctl->ahead[sh * 32]) >= hi - lo) continue;  // dry: no atomic
-    const uint32_t c = atomicAdd(&ctl->ahead[sh * 32], 1u);
-    if (c < hi - lo) return lo + c;
+// A group of W lanes of a wave64 that walks one root: the whole wave, or one of its four 16-lane
+// quarters.  Masks are the group's bits of a ballot, lane numbers count from the group's first lane.
+template <int W>
+struct Lanes {
+  static_assert(W == 64 || W == 16, "a wave or a quarter of one");
+  static constexpr int width = W;
+  using Mask = std::conditional_t<W == 64, uint64_t, uint32_t>;
+  static __device__ __forceinline__ int lane() { return lane_id() & (W - 1); }
+  static __device__ __forceinline__ int base() { return lane_id() & ~(W - 1); }
+  static __device__ __forceinline__ Mask ballot(bool pred) {
+    if constexpr (W == 64) return __ballot(pred);
+    else return (uint32_t)(__ballot(pred) >> base()) & ((1u << W) - 1);
+  }
+  static __device__ __forceinline__ uint32_t below(Mask m) {  // set bits below this lane
+    if constexpr (W == 64) return lanes_below(m);
+    else return (uint32_t)__popc(m & ((1u << lane()) - 1));
+  }
+  static __device__ __forceinline__ uint32_t first(Mask m) {  // m != 0
+    if constexpr (W == 64) return (uint32_t)(__ffsll((unsigned long long)m) - 1);
+    else return (uint32_t)(__ffs(m) - 1);
+  }
+  static __device__ __forceinline__ uint32_t count(Mask m) {
+    if constexpr (W == 64) return (uint32_t)__popcll(m);
+    else return (uint32_t)__popc(m);
+  }
+  static __device__ __forceinline__ uint32_t shfl(uint32_t v, uint32_t p) { return __shfl(v, base() + (int)p, 64); }
+  static __device__ __forceinline__ uint64_t shfl(uint64_t v, uint32_t p) {
+    return ((uint64_t)shfl((uint32_t)(v >> 32), p) << 32) | shfl((uint32_t)v, p);
+  }
+};
+
+// `count` items cut into 8 ranges, each claimed through a head of its own on a 128-B line of its own
+// (heads[range * 32]): the range of this workgroup's XCD label first, then the others; a range seen dry
+// costs no atomic.  A cursor that is kept never returns to a range it left.  NONE: all eight are used up.
+struct RangeCursor {
+  uint32_t at, tried;
+};
+__device__ __forceinline__ RangeCursor range_cursor() { return RangeCursor{blockIdx.x & 7, 0}; }
+__device__ __forceinline__ uint32_t claim_ranged(uint32_t* heads, uint32_t count, RangeCursor& rc) {
+  const uint32_t per = (count + 7) / 8;
+  for (; rc.tried < 8; rc.tried++, rc.at = (rc.at + 1) & 7) {
+    const uint32_t lo = rc.at * per, hi = min(count, lo + per);
+    if (lo >= hi || ld_sc1(&heads[rc.at * 32]) >= hi - lo) continue;
+    const uint32_t k = atomicAdd(&heads[rc.at * 32], 1u);
+    if (k < hi - lo) return lo + k;
   }
   return NONE;
+}
+
+// A free arena chunk (one lane only), or NONE.
+__device__ __forceinline__ uint32_t claim_chunk(ExpCtl* ctl, uint32_t n_chunks) {
+  RangeCursor rc = range_cursor();
+  return claim_ranged(ctl->ahead, n_chunks, rc);
 }
 
 // Per-root result of the DFS: first chunk and record count (0 records = nil tree).
@@ -101,35 +151,37 @@ struct Stream {
   uint32_t* next;  // chunk -> next chunk
   uint32_t n_chunks;
   ExpCtl* ctl;
-  uint32_t first, cur, pos;  // wave-uniform
+  uint32_t first, cur, pos;  // the same in every lane of the group G that writes the stream
   bool ok;
 };
 
+// A fresh chunk, not yet linked to the stream; NONE (and !S.ok) when the arena is used up.
+template <class G>
 __device__ __forceinline__ uint32_t alloc_chunk(Stream& S) {
   uint32_t c = 0;
-  if (lane_id() == 0) c = claim_chunk(S.ctl, S.n_chunks);
-  c = __shfl(c, 0, 64);
+  if (G::lane() == 0) c = claim_chunk(S.ctl, S.n_chunks);
+  c = G::shfl(c, 0);
   if (c >= S.n_chunks) {
-    if (lane_id() == 0) S.ctl->overflow = 1;
+    if (G::lane() == 0) S.ctl->overflow = 1;
     S.ok = false;
     return NONE;
   }
-  if (lane_id() == 0) S.next[c] = NONE;
+  if (G::lane() == 0) S.next[c] = NONE;
   return c;
 }
 
-// Lanes with `pred` append one record each, in lane order, to the wave's stream.
+// Lanes with `pred` append one record each, in lane order, to the group's stream.
+template <class G>
 __device__ __forceinline__ void emit(Stream& S, bool pred, const kg_tree_node& r) {
-  const uint64_t m = __ballot(pred);
+  const typename G::Mask m = G::ballot(pred);
   if (!m || !S.ok) return;
-  const uint32_t cnt = __popcll(m);
-  const uint32_t rank = lanes_below(m);
-  uint32_t room = CHUNK - S.pos;
+  const uint32_t cnt = G::count(m), rank = G::below(m);
+  const uint32_t room = CHUNK - S.pos;
   uint32_t nxt = NONE;
   if (cnt > room) {
-    nxt = alloc_chunk(S);
+    nxt = alloc_chunk<G>(S);
     if (!S.ok) return;
-    if (lane_id() == 0) S.next[S.cur] = nxt;
+    if (G::lane() == 0) S.next[S.cur] = nxt;
   }
   if (pred) {
     if (rank < room) S.arena[(size_t)S.cur * CHUNK + S.pos + rank] = r;
@@ -169,344 +221,82 @@ __device__ __forceinline__ kg_tree_node rec_subject(const DevSnap& s, uint32_t s
 
 enum : int { EXP_OK = 0, EXP_OVERFLOW = 1, EXP_ARENA = 2 };
 
-template <class Store>
-__device__ int expand_root(const DevSnap& s, Store& st, const kg_set& root, int32_t global, ExpFrame* stack,
-                           Stream& S, uint32_t& n_records) {
-  const int lane = lane_id();
-  S.ok = true;
-  S.pos = 0;
-  S.first = S.cur = alloc_chunk(S);
-  n_records = 0;
-  if (!S.ok) return EXP_ARENA;
-  int32_t d = root.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:37-39
-  if (root.sns == KG_SUBJECT_ID) {       // SubjectID -> Leaf
-    emit(S, lane == 0, rec_subject(s, root.sobj < 0x7FFFFFFFu ? root.sobj : 0x7FFFFFFFu));
-    n_records = 1;
-    return S.ok ? EXP_OK : EXP_ARENA;
-  }
-  const uint32_t rn = nmap_find(s, root.sns, root.srel, root.sobj);
-  if (rn == NONE) return EXP_OK;  // no rows anywhere: nil
-  st.reset();
-  uint32_t n_vis = 0;
-  wave_add_roots(st, lane == 0, rn, n_vis);  // marks the root visited
-  const uint64_t rb0 = s.row_off[rn], re0 = s.row_off[rn + 1];
-  if (rb0 == re0) {
-    st.finish(n_vis);
-    return EXP_OK;  // no rows: nil
-  }
-  if (d <= 1) {
-    emit(S, lane == 0, rec_set(s, 2, rn, 0));
-    st.finish(n_vis);
-    n_records = 1;
-    return S.ok ? EXP_OK : EXP_ARENA;
-  }
-  emit(S, lane == 0, rec_set(s, 1, rn, (uint32_t)(re0 - rb0)));
-  uint32_t count = 1;
-  int sp = 0;
-  ExpFrame F{rb0, rn, 0, (uint32_t)(re0 - rb0), d};
-  int status = EXP_OK;
-  for (;;) {
-    const uint64_t rb = F.rb, re = F.rb + F.len;
-    const bool can_expand = F.d - 1 >= 2;
-    bool pushed = false;
-    while (rb + F.cursor < re) {
-      const uint64_t i = rb + F.cursor + lane;
-      const bool valid = i < re;
-      const uint32_t sub = valid ? s.row_subj[i] : 0;
-      bool cand = false;
-      uint64_t crb = 0, cre = 0;
-      if (valid && can_expand && (sub & SET_BIT)) {
-        const uint32_t c = sub & ~SET_BIT;
-        crb = s.row_off[c];
-        cre = s.row_off[c + 1];
-        // a set visited before this chunk is a leaf whatever comes first (the visited set only
-        // grows): only unvisited sets with rows are order-dependent candidates, taken one by one.
-        // The visited lookup does not wait for the row range (both depend on the subject only).
-        const bool seen = st.contains(c);
-        cand = cre > crb && !seen;
-      }
-      const uint64_t mc = __ballot(cand);
-      const uint32_t p = mc ? (uint32_t)(__ffsll((unsigned long long)mc) - 1) : 64u;
-      // everything before the first candidate: leaves (and marks, order-free for non-candidates)
-      const bool leaf = valid && (uint32_t)lane < p;
-      // d-1 <= 1: child sets become leaves but BuildTree still marks them visited, which a later
-      // (shallower) encounter elsewhere in the tree observes.  Sets without rows need no mark:
-      // any encounter of them is a leaf.  SubjectIDs are never marked (engine.go:41-45).
-      if (!can_expand && !wave_add_roots(st, leaf && (sub & SET_BIT), sub & ~SET_BIT, n_vis)) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      emit(S, leaf, rec_subject(s, sub));
-      count += __popcll(__ballot(leaf));
-      if (!S.ok) return EXP_ARENA;
-      if (p == 64u) {
-        F.cursor += (uint32_t)min<uint64_t>(64, re - (rb + F.cursor));
-        continue;
-      }
-      // candidate at lane p, in order
-      const uint32_t csub = __shfl(sub, (int)p, 64);
-      const uint32_t cnode = csub & ~SET_BIT;
-      const uint32_t clen = (uint32_t)(__shfl((uint32_t)(cre - crb), (int)p, 64));
-      const uint64_t cbeg = ((uint64_t)(uint32_t)__shfl((uint32_t)(crb >> 32), (int)p, 64) << 32) |
-                            (uint32_t)__shfl((uint32_t)crb, (int)p, 64);
-      F.cursor += p + 1;
-      const uint32_t before = n_vis;
-      if (!wave_add_roots(st, lane == 0, cnode, n_vis)) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      if (n_vis == before) {  // already visited: BuildTree -> nil -> Leaf{row subject}
-        emit(S, lane == 0, rec_subject(s, csub));
-        count++;
-        if (!S.ok) return EXP_ARENA;
-        continue;
-      }
-      emit(S, lane == 0, rec_set(s, 1, cnode, clen));
-      count++;
-      if (!S.ok) return EXP_ARENA;
-      if (sp >= 0x7FFF) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      if (lane == 0) stack[sp] = F;
-      sp++;
-      F = ExpFrame{cbeg, cnode, 0, clen, F.d - 1};
-      pushed = true;
-      break;
+// ------------------------------------------------------------------ the walk's policies
+// A policy gives expand_walk the three things its instantiations differ in:
+//   fetch / leaf_rec / union_rec   a group-wide chunk of a frame's row: per lane `valid`, the row subject,
+//                                  the child set's row range, and what the records are built from;
+//   reset / mark / unseen / take   the visited set (mark, take: false when its capacity would be passed;
+//   / room / finish                room: false when the root has too many records for this pass);
+//   push / pop / max_sp            where frames live.
+
+// The plain chunk: row subjects behind `valid`, a child's row range only where it can be a candidate;
+// records read nd_* when they are emitted.  Frames go to a stack in HBM.
+template <class G>
+struct PlainChunks {
+  ExpFrame* stack;
+  int max_sp;
+  struct Chunk {
+    bool valid;
+    uint32_t width, sub, clen;
+    uint64_t crb;
+  };
+  __device__ __forceinline__ Chunk fetch(const DevSnap& s, int, uint64_t at0, uint64_t re, bool can_expand) const {
+    Chunk c{};
+    c.width = (uint32_t)min<uint64_t>(G::width, re - at0);
+    c.valid = (uint32_t)G::lane() < c.width;
+    c.sub = c.valid ? s.row_subj[at0 + G::lane()] : 0;
+    if (c.valid && can_expand && (c.sub & SET_BIT)) {
+      const uint32_t n = c.sub & ~SET_BIT;
+      c.crb = s.row_off[n];
+      c.clen = (uint32_t)(s.row_off[n + 1] - c.crb);
     }
-    if (status != EXP_OK) break;
-    if (pushed) continue;
-    if (sp == 0) break;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    sp--;
-    F = stack[sp];
+    return c;
   }
-  st.finish((uint32_t)min<uint64_t>(n_vis, st.cap()));
-  n_records = count;
-  return status;
-}
-
-
-
-// Passes 2 and 3 hold the batch's largest roots, whose walks are the batch's tail: one wave doing
-// hundreds of thousands of dependent round trips (C5's largest tree: 335 k records, ~135 ms).  This
-// variant of expand_root cuts the trips per expanded set:
-//   * a chunk scan issues the child's row range, its node triple (for the record) and the visited
-//     lookup in ONE round trip after the row_subj load, so leaves are emitted from registers;
-//   * the frame stack and each frame's scanned chunk live in LDS (XF frames: C5's depth-5 walk needs
-//     7), so a pop resumes the parent's chunk without re-reading row_subj / row_off / nd_* -- only the
-//     visited lookups are redone (the set grew during the subtree);
-//   * the candidate's insert is a plain store into the empty slot its lookup found (the table belongs
-//     to this wave and nothing was inserted in between): no CAS round trip before the push.
-// Output is identical to expand_root (same candidates in the same order).
-constexpr int XF = 16;
-struct ExpLds {
-  ExpFrame fr[XF];
-  uint64_t cbase[XF];  // row position of lane 0 of the frame's cached chunk
-  uint32_t cn[XF];     // cached lanes (0: none)
-  uint32_t sub[XF][64], clen[XF][64], ns[XF][64], obj[XF][64], rel[XF][64];
-  uint64_t crb[XF][64];
+  __device__ __forceinline__ kg_tree_node leaf_rec(const DevSnap& s, const Chunk& c) const { return rec_subject(s, c.sub); }
+  __device__ __forceinline__ kg_tree_node union_rec(const DevSnap& s, const Chunk&, uint32_t, uint32_t node,
+                                                    uint32_t len) const {
+    return rec_set(s, 1, node, len);
+  }
+  __device__ __forceinline__ void push(int sp, const ExpFrame& F) const {
+    if (G::lane() == 0) stack[sp] = F;
+  }
+  __device__ __forceinline__ ExpFrame pop(int sp) const { return stack[sp]; }
 };
 
+// A visited store with a list of its keys (kg_bfs.h: LdsStore, HashStore, GlobalStore).
 template <class Store>
-__device__ int expand_root_x(const DevSnap& s, Store& st, const kg_set& root, int32_t global, ExpFrame* gstack,
-                             Stream& S, uint32_t& n_records, ExpLds& X) {
-  const int lane = lane_id();
-  S.ok = true;
-  S.pos = 0;
-  S.first = S.cur = alloc_chunk(S);
-  n_records = 0;
-  if (!S.ok) return EXP_ARENA;
-  int32_t d = root.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:37-39
-  if (root.sns == KG_SUBJECT_ID) {       // SubjectID -> Leaf
-    emit(S, lane == 0, rec_subject(s, root.sobj < 0x7FFFFFFFu ? root.sobj : 0x7FFFFFFFu));
-    n_records = 1;
-    return S.ok ? EXP_OK : EXP_ARENA;
+struct ListedVisits {
+  Store& st;
+  uint32_t n_vis;
+  __device__ __forceinline__ void reset() {
+    st.reset();
+    n_vis = 0;
   }
-  const uint32_t rn = nmap_find(s, root.sns, root.srel, root.sobj);
-  if (rn == NONE) return EXP_OK;  // no rows anywhere: nil
-  st.reset();
-  uint32_t n_vis = 0;
-  wave_add_roots(st, lane == 0, rn, n_vis);  // marks the root visited
-  const uint64_t rb0 = s.row_off[rn], re0 = s.row_off[rn + 1];
-  if (rb0 == re0) {
-    st.finish(n_vis);
-    return EXP_OK;
-  }
-  if (d <= 1) {
-    emit(S, lane == 0, rec_set(s, 2, rn, 0));
-    st.finish(n_vis);
-    n_records = 1;
-    return S.ok ? EXP_OK : EXP_ARENA;
-  }
-  emit(S, lane == 0, rec_set(s, 1, rn, (uint32_t)(re0 - rb0)));
-  uint32_t count = 1;
-  int sp = 0;
-  if (lane < XF) X.cn[lane] = 0;
-  __builtin_amdgcn_wave_barrier();
-  ExpFrame F{rb0, rn, 0, (uint32_t)(re0 - rb0), d};
-  int status = EXP_OK;
-  for (;;) {
-    const uint64_t rb = F.rb, re = F.rb + F.len;
-    const bool can_expand = F.d - 1 >= 2;
-    bool pushed = false;
-    while (rb + F.cursor < re) {
-      const uint64_t at0 = rb + F.cursor;
-      // the chunk: the rest of this frame's cached chunk if the cursor is inside it, else a fresh one
-      const bool cached = sp < XF && X.cn[sp] && at0 >= X.cbase[sp] && at0 < X.cbase[sp] + X.cn[sp];
-      uint32_t sub = 0, clen = 0, nns = 0, nobj = 0, nrel = 0;
-      uint64_t crb = 0;
-      bool valid;
-      uint32_t width;
-      if (cached) {
-        const uint32_t k0 = (uint32_t)(at0 - X.cbase[sp]);
-        width = X.cn[sp] - k0;
-        valid = (uint32_t)lane < width;
-        const uint32_t k = valid ? k0 + lane : 0u;
-        sub = X.sub[sp][k];
-        clen = X.clen[sp][k];
-        crb = X.crb[sp][k];
-        nns = X.ns[sp][k];
-        nobj = X.obj[sp][k];
-        nrel = X.rel[sp][k];
-      } else {
-        width = (uint32_t)min<uint64_t>(64, re - at0);
-        valid = (uint32_t)lane < width;
-        sub = s.row_subj[valid ? at0 + lane : at0];
-        const bool set = valid && (sub & SET_BIT);
-        const uint32_t c = set ? sub & ~SET_BIT : 0u;  // node 0 exists: unconditional loads, no waits in branches
-        const uint64_t r0 = s.row_off[c], r1 = s.row_off[c + 1];
-        nns = s.nd_ns[c];
-        nobj = s.nd_obj[c];
-        nrel = s.nd_rel[c];
-        crb = set ? r0 : 0;
-        clen = set ? (uint32_t)(r1 - r0) : 0u;
-        if (sp < XF) {
-          X.sub[sp][lane] = sub;
-          X.clen[sp][lane] = clen;
-          X.crb[sp][lane] = crb;
-          X.ns[sp][lane] = nns;
-          X.obj[sp][lane] = nobj;
-          X.rel[sp][lane] = nrel;
-          if (lane == 0) {
-            X.cbase[sp] = at0;
-            X.cn[sp] = width;
-          }
-        }
-      }
-      const bool is_set = valid && (sub & SET_BIT);
-      const uint32_t c = sub & ~SET_BIT;
-      bool cand = false;
-      uint32_t vat = 0;
-      if (is_set && can_expand) {
-        // a set visited before this chunk is a leaf whatever comes first (the visited set only
-        // grows): only unvisited sets with rows are order-dependent candidates, taken one by one
-        const bool seen = st.find(c, vat);
-        cand = clen > 0 && !seen;
-      }
-      const uint64_t mc = __ballot(cand);
-      const uint32_t p = mc ? (uint32_t)(__ffsll((unsigned long long)mc) - 1) : 64u;
-      // everything before the first candidate: leaves (and marks, order-free for non-candidates)
-      const bool leaf = valid && (uint32_t)lane < p;
-      // d-1 <= 1: child sets become leaves but BuildTree still marks them visited, which a later
-      // (shallower) encounter elsewhere in the tree observes.  SubjectIDs are never marked.
-      if (!can_expand && !wave_add_roots(st, leaf && is_set, c, n_vis)) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      kg_tree_node r;
-      r.type = 2;
-      r.pad = 0;
-      r.n_children = 0;
-      r.is_set = is_set ? 1 : 0;
-      r.ns = is_set ? nns : KG_SUBJECT_ID;
-      r.obj = is_set ? nobj : sub;
-      r.rel = is_set ? nrel : 0u;
-      emit(S, leaf, r);
-      count += __popcll(__ballot(leaf));
-      if (!S.ok) return EXP_ARENA;
-      if (p == 64u) {
-        F.cursor += width;
-        continue;
-      }
-      // candidate at lane p, in order: unvisited when its lookup ran, and nothing was inserted since
-      const uint32_t cnode = __shfl(c, (int)p, 64);
-      const uint32_t cl = __shfl(clen, (int)p, 64);
-      const uint32_t cat = __shfl(vat, (int)p, 64);
-      const uint64_t cbeg = ((uint64_t)(uint32_t)__shfl((uint32_t)(crb >> 32), (int)p, 64) << 32) |
-                            (uint32_t)__shfl((uint32_t)crb, (int)p, 64);
-      kg_tree_node u;
-      u.type = 1;
-      u.is_set = 1;
-      u.pad = 0;
-      u.ns = __shfl(nns, (int)p, 64);
-      u.obj = __shfl(nobj, (int)p, 64);
-      u.rel = __shfl(nrel, (int)p, 64);
-      u.n_children = cl;
-      F.cursor += p + 1;
-      if (n_vis + 1 > st.cap()) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      if (lane == 0) {
-        st.put_new(cnode, cat);
-        st.list()[n_vis] = cnode;
-      }
-      n_vis++;
-      emit(S, lane == 0, u);
-      count++;
-      if (!S.ok) return EXP_ARENA;
-      if (sp >= 0x7FFF) {
-        status = EXP_OVERFLOW;
-        break;
-      }
-      if (lane == 0) {
-        if (sp < XF) X.fr[sp] = F;
-        else gstack[sp] = F;
-      }
-      sp++;
-      if (lane == 0 && sp < XF) X.cn[sp] = 0;  // the child frame starts without a cached chunk
-      __builtin_amdgcn_wave_barrier();
-      F = ExpFrame{cbeg, cnode, 0, cl, F.d - 1};
-      pushed = true;
-      break;
-    }
-    if (status != EXP_OK) break;
-    if (pushed) continue;
-    if (sp == 0) break;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    sp--;
-    F = sp < XF ? X.fr[sp] : gstack[sp];
-  }
-  st.finish((uint32_t)min<uint64_t>(n_vis, st.cap()));
-  n_records = count;
-  return status;
-}
+  __device__ __forceinline__ bool mark(bool offer, uint32_t node) { return wave_add_roots(st, offer, node, n_vis); }
+  __device__ __forceinline__ bool room(uint32_t) const { return true; }
+  __device__ __forceinline__ void finish() { st.finish((uint32_t)min<uint64_t>(n_vis, st.cap())); }
+};
 
-// ------------------------------------------------------------------ pass 0: 16-lane walkers (round 6)
-// C5's ~100 k hot roots average ~45 records (a handful of expanded sets each): one 64-lane wave per
-// root left most lanes idle on every row chunk and paid a whole wave's chain of dependent round trips
-// per root.  Here a wave runs FOUR roots at once, one per 16-lane group, with expand_root's exact
-// pre-order (the same chunk scan, 16 entries at a time, first-candidate rule, one visited set per
-// request).  Each walker has its own LDS visited hash and record stream; a root that outgrows the
-// small hash or SW_RECS records is given up (its chunks are abandoned) and redone by the 64-lane pass.
+// Pass 1: the wave's LDS hash.
+struct LdsPolicy : PlainChunks<Lanes<64>>, ListedVisits<LdsStore> {
+  __device__ __forceinline__ bool unseen(uint32_t node, uint32_t&) const { return !st.contains(node); }
+  __device__ __forceinline__ bool take(uint32_t node, uint32_t) { return mark(lane_id() == 0, node); }
+};
+
+// Pass 0 (round 6).  C5's ~100 k hot roots average ~45 records (a handful of expanded sets each): one
+// 64-lane wave per root left most lanes idle on every row chunk and paid a whole wave's chain of
+// dependent round trips per root.  Here a wave runs FOUR roots at once, one per 16-lane group.  Each
+// walker has its own LDS visited hash and record stream; a root that outgrows the small hash or SW_RECS
+// records is given up (its chunks are abandoned) and redone by the 64-lane pass.
 constexpr int SW = 16;
 constexpr int SW_VL2 = 9;           // visited-hash slots per walker (512)
 constexpr uint32_t SW_CAP = 224;    // visited sets per walker (hash load <= ~0.5)
 constexpr uint32_t SW_RECS = 2048;  // records per root before it is handed to the 64-lane pass
-__device__ __forceinline__ int sw_lane() { return lane_id() & (SW - 1); }
-__device__ __forceinline__ int sw_base() { return lane_id() & ~(SW - 1); }
-__device__ __forceinline__ uint32_t sw_bits(uint64_t m) { return (uint32_t)(m >> sw_base()) & 0xFFFFu; }
-__device__ __forceinline__ uint32_t sw_below(uint32_t m) { return (uint32_t)__popc(m & ((1u << sw_lane()) - 1)); }
 
 struct SubStore {
   uint32_t* vis;  // 1 << SW_VL2 slots
   __device__ void reset() const {
-    for (int i = sw_lane() * 4; i < (1 << SW_VL2); i += SW * 4)
+    for (int i = Lanes<SW>::lane() * 4; i < (1 << SW_VL2); i += SW * 4)
       *reinterpret_cast<uint4*>(&vis[i]) = make_uint4(NONE, NONE, NONE, NONE);
     __builtin_amdgcn_wave_barrier();
   }
@@ -532,145 +322,255 @@ struct SubStore {
   }
 };
 
-// group-uniform values: S.cur / S.pos / S.first / S.ok are the same in the walker's 16 lanes
-__device__ __forceinline__ uint32_t sw_alloc_chunk(Stream& S) {
-  uint32_t c = 0;
-  if (sw_lane() == 0) c = claim_chunk(S.ctl, S.n_chunks);
-  c = __shfl(c, sw_base(), 64);
-  if (c >= S.n_chunks) {
-    if (sw_lane() == 0) S.ctl->overflow = 1;
-    S.ok = false;
-    return NONE;
+struct SubPolicy : PlainChunks<Lanes<SW>> {
+  SubStore st;
+  uint32_t n_vis;
+  __device__ __forceinline__ void reset() {
+    st.reset();
+    n_vis = 0;
   }
-  if (sw_lane() == 0) S.next[c] = NONE;
-  return c;
-}
+  __device__ __forceinline__ bool mark(bool offer, uint32_t node) {  // counted, not listed
+    const bool fresh = offer && st.insert(node);
+    const uint32_t cnt = Lanes<SW>::count(Lanes<SW>::ballot(fresh));
+    if (n_vis + cnt > SW_CAP) return false;
+    n_vis += cnt;
+    return true;
+  }
+  __device__ __forceinline__ bool unseen(uint32_t node, uint32_t&) const { return !st.contains(node); }
+  __device__ __forceinline__ bool take(uint32_t node, uint32_t) { return mark(Lanes<SW>::lane() == 0, node); }
+  __device__ __forceinline__ bool room(uint32_t count) const { return count <= SW_RECS; }
+  __device__ __forceinline__ void finish() const {}
+};
 
-__device__ __forceinline__ void sw_emit(Stream& S, bool pred, const kg_tree_node& r) {
-  const uint32_t m = sw_bits(__ballot(pred));
-  if (!m || !S.ok) return;
-  const uint32_t cnt = (uint32_t)__popc(m), rank = sw_below(m);
-  const uint32_t room = CHUNK - S.pos;
-  uint32_t nxt = NONE;
-  if (cnt > room) {
-    nxt = sw_alloc_chunk(S);
-    if (!S.ok) return;
-    if (sw_lane() == 0) S.next[S.cur] = nxt;
-  }
-  if (pred) {
-    if (rank < room) S.arena[(size_t)S.cur * CHUNK + S.pos + rank] = r;
-    else S.arena[(size_t)nxt * CHUNK + (rank - room)] = r;
-  }
-  if (cnt > room) {
-    S.cur = nxt;
-    S.pos = cnt - room;
-  } else {
-    S.pos += cnt;
-  }
-}
+// The hash pass and pass 3 hold the batch's largest roots, whose walks are the batch's tail: one wave
+// doing hundreds of thousands of dependent round trips (C5's largest tree: 335 k records, ~135 ms).
+// This policy cuts the trips per expanded set:
+//   * a chunk scan issues the child's row range, its node triple (for the record) and the visited
+//     lookup in ONE round trip after the row_subj load, so leaves are emitted from registers;
+//   * the frame stack and each frame's scanned chunk live in LDS (XF frames: C5's depth-5 walk needs
+//     7), so a pop resumes the parent's chunk without re-reading row_subj / row_off / nd_* -- only the
+//     visited lookups are redone (the set grew during the subtree);
+//   * the candidate's insert is a plain store into the empty slot its lookup found (the table belongs
+//     to this wave and nothing was inserted in between): no CAS round trip before the push.
+constexpr int XF = 16;
+struct ExpLds {
+  ExpFrame fr[XF];
+  uint64_t cbase[XF];  // row position of lane 0 of the frame's cached chunk
+  uint32_t cn[XF];     // cached lanes (0: none)
+  uint32_t sub[XF][64], clen[XF][64], ns[XF][64], obj[XF][64], rel[XF][64];
+  uint64_t crb[XF][64];
+};
 
-// marks `node` (lanes with `offer`); false when the walker's visited cap would be passed
-__device__ __forceinline__ bool sw_add(const SubStore& st, bool offer, uint32_t node, uint32_t& n_vis) {
-  const bool fresh = offer && st.insert(node);
-  const uint32_t cnt = (uint32_t)__popc(sw_bits(__ballot(fresh)));
-  if (n_vis + cnt > SW_CAP) return false;
-  n_vis += cnt;
-  return true;
-}
+template <class Store>
+struct CachedPolicy : ListedVisits<Store> {
+  using ListedVisits<Store>::st;
+  using ListedVisits<Store>::n_vis;
+  ExpLds& X;
+  ExpFrame* gstack;
+  static constexpr int max_sp = 0x7FFF;
+  struct Chunk {
+    bool valid;
+    uint32_t width, sub, clen, ns, obj, rel;
+    uint64_t crb;
+  };
+  __device__ __forceinline__ void reset() {
+    ListedVisits<Store>::reset();
+    if (lane_id() < XF) X.cn[lane_id()] = 0;
+    __builtin_amdgcn_wave_barrier();
+  }
+  // the rest of frame sp's cached chunk if the cursor is inside it, else a fresh one
+  __device__ __forceinline__ Chunk fetch(const DevSnap& s, int sp, uint64_t at0, uint64_t re, bool) const {
+    const int lane = lane_id();
+    const bool cached = sp < XF && X.cn[sp] && at0 >= X.cbase[sp] && at0 < X.cbase[sp] + X.cn[sp];
+    Chunk c;
+    if (cached) {
+      const uint32_t k0 = (uint32_t)(at0 - X.cbase[sp]);
+      c.width = X.cn[sp] - k0;
+      c.valid = (uint32_t)lane < c.width;
+      const uint32_t k = c.valid ? k0 + lane : 0u;
+      c.sub = X.sub[sp][k];
+      c.clen = X.clen[sp][k];
+      c.crb = X.crb[sp][k];
+      c.ns = X.ns[sp][k];
+      c.obj = X.obj[sp][k];
+      c.rel = X.rel[sp][k];
+    } else {
+      c.width = (uint32_t)min<uint64_t>(64, re - at0);
+      c.valid = (uint32_t)lane < c.width;
+      c.sub = s.row_subj[c.valid ? at0 + lane : at0];
+      const bool set = c.valid && (c.sub & SET_BIT);
+      const uint32_t n = set ? c.sub & ~SET_BIT : 0u;  // node 0 exists: unconditional loads, no waits in branches
+      const uint64_t r0 = s.row_off[n], r1 = s.row_off[n + 1];
+      c.ns = s.nd_ns[n];
+      c.obj = s.nd_obj[n];
+      c.rel = s.nd_rel[n];
+      c.crb = set ? r0 : 0;
+      c.clen = set ? (uint32_t)(r1 - r0) : 0u;
+      if (sp < XF) {
+        X.sub[sp][lane] = c.sub;
+        X.clen[sp][lane] = c.clen;
+        X.crb[sp][lane] = c.crb;
+        X.ns[sp][lane] = c.ns;
+        X.obj[sp][lane] = c.obj;
+        X.rel[sp][lane] = c.rel;
+        if (lane == 0) {
+          X.cbase[sp] = at0;
+          X.cn[sp] = c.width;
+        }
+      }
+    }
+    return c;
+  }
+  __device__ __forceinline__ kg_tree_node leaf_rec(const DevSnap&, const Chunk& c) const {
+    const bool is_set = c.valid && (c.sub & SET_BIT);
+    kg_tree_node r;
+    r.type = 2;
+    r.pad = 0;
+    r.n_children = 0;
+    r.is_set = is_set ? 1 : 0;
+    r.ns = is_set ? c.ns : KG_SUBJECT_ID;
+    r.obj = is_set ? c.obj : c.sub;
+    r.rel = is_set ? c.rel : 0u;
+    return r;
+  }
+  __device__ __forceinline__ kg_tree_node union_rec(const DevSnap&, const Chunk& c, uint32_t p, uint32_t,
+                                                    uint32_t len) const {
+    kg_tree_node u;
+    u.type = 1;
+    u.is_set = 1;
+    u.pad = 0;
+    u.ns = __shfl(c.ns, (int)p, 64);
+    u.obj = __shfl(c.obj, (int)p, 64);
+    u.rel = __shfl(c.rel, (int)p, 64);
+    u.n_children = len;
+    return u;
+  }
+  __device__ __forceinline__ bool unseen(uint32_t node, uint32_t& at) const { return !st.find(node, at); }
+  // the candidate was unvisited when its lookup ran and nothing was inserted since: a plain store
+  __device__ __forceinline__ bool take(uint32_t node, uint32_t at) {
+    if (n_vis + 1 > st.cap()) return false;
+    if (lane_id() == 0) {
+      st.put_new(node, at);
+      st.list()[n_vis] = node;
+    }
+    n_vis++;
+    return true;
+  }
+  // (two conditions, not if / else: the compiler folds an if / else of the same frame into ONE store
+  // through a selected pointer, LDS or HBM, which is a flat store on every push)
+  __device__ __forceinline__ void push(int sp, const ExpFrame& F) const {
+    if (lane_id() == 0 && sp >= XF) gstack[sp] = F;
+    if (lane_id() == 0 && sp < XF) {
+      X.fr[sp] = F;
+      if (sp + 1 < XF) X.cn[sp + 1] = 0;  // the child frame starts without a cached chunk
+    }
+    __builtin_amdgcn_wave_barrier();
+  }
+  __device__ __forceinline__ ExpFrame pop(int sp) const { return sp < XF ? X.fr[sp] : gstack[sp]; }
+};
 
-// expand_root (above) on one 16-lane walker: identical records in identical order, or EXP_OVERFLOW
-__device__ int expand_root_sw(const DevSnap& s, const SubStore& st, const kg_set& root, int32_t global,
-                              ExpFrame* stack, uint32_t stack_cap, Stream& S, uint32_t& n_records) {
-  const int gl = sw_lane(), gb = sw_base();
+// ------------------------------------------------------------------ the walk
+// BuildTree's pre-order walk of one root on the lane group G: identical records in identical order in
+// every instantiation, or EXP_OVERFLOW when the root outgrows the policy's stores (it is redone by the
+// next pass; the chunks written so far are abandoned).  n_records: 0 = a nil tree.
+// The policy comes by value: a few pointers and the visited count, which then is a local of this walk
+// (by reference it cost 2-4 VGPRs).  The root prologue returns from here directly: as a function of
+// its own that hands back "done" or the first frame it cost k_expand_hash ~140 more SGPR spill
+// reloads and 2-3 % of its time.
+template <class G, class P>
+__device__ int expand_walk(const DevSnap& s, P pol, const kg_set& root, int32_t global, Stream& S,
+                           uint32_t& n_records) {
+  // the root: what BuildTree does before it looks at a row (the depth clamp, SubjectID -> Leaf, no node
+  // or no rows -> nil, no depth left -> Leaf), else the root's union record and its frame
+  const bool first = G::lane() == 0;
   S.ok = true;
   S.pos = 0;
-  S.first = S.cur = sw_alloc_chunk(S);
+  S.first = S.cur = alloc_chunk<G>(S);
   n_records = 0;
   if (!S.ok) return EXP_ARENA;
-  int32_t d = root.max_depth;
-  if (d <= 0 || global < d) d = global;  // engine.go:37-39
-  if (root.sns == KG_SUBJECT_ID) {       // SubjectID -> Leaf
-    sw_emit(S, gl == 0, rec_subject(s, root.sobj < 0x7FFFFFFFu ? root.sobj : 0x7FFFFFFFu));
+  const int32_t d = clamp_depth(root.max_depth, global);  // engine.go:37-39
+  if (root.sns == KG_SUBJECT_ID) {                        // SubjectID -> Leaf
+    emit<G>(S, first, rec_subject(s, root.sobj < 0x7FFFFFFFu ? root.sobj : 0x7FFFFFFFu));
     n_records = 1;
     return S.ok ? EXP_OK : EXP_ARENA;
   }
   const uint32_t rn = nmap_find(s, root.sns, root.srel, root.sobj);
   if (rn == NONE) return EXP_OK;  // no rows anywhere: nil
-  st.reset();
-  uint32_t n_vis = 0;
-  sw_add(st, gl == 0, rn, n_vis);  // marks the root visited
+  pol.reset();
+  pol.mark(first, rn);
   const uint64_t rb0 = s.row_off[rn], re0 = s.row_off[rn + 1];
-  if (rb0 == re0) return EXP_OK;  // no rows: nil
-  if (d <= 1) {
-    sw_emit(S, gl == 0, rec_set(s, 2, rn, 0));
+  if (rb0 == re0) {  // no rows: nil
+    pol.finish();
+    return EXP_OK;
+  }
+  if (d <= 1) {  // no depth left: a leaf
+    emit<G>(S, first, rec_set(s, 2, rn, 0));
+    pol.finish();
     n_records = 1;
     return S.ok ? EXP_OK : EXP_ARENA;
   }
-  sw_emit(S, gl == 0, rec_set(s, 1, rn, (uint32_t)(re0 - rb0)));
-  uint32_t count = 1;
-  uint32_t sp = 0;
+  emit<G>(S, first, rec_set(s, 1, rn, (uint32_t)(re0 - rb0)));
   ExpFrame F{rb0, rn, 0, (uint32_t)(re0 - rb0), d};
   int status = EXP_OK;
+  uint32_t count = 1;
+  int sp = 0;
   for (;;) {
     const uint64_t rb = F.rb, re = F.rb + F.len;
     const bool can_expand = F.d - 1 >= 2;
     bool pushed = false;
     while (rb + F.cursor < re) {
-      if (count > SW_RECS) {
+      if (!pol.room(count)) {
         status = EXP_OVERFLOW;
         break;
       }
-      const uint64_t i = rb + F.cursor + gl;
-      const bool valid = i < re;
-      const uint32_t sub = valid ? s.row_subj[i] : 0;
+      const auto c = pol.fetch(s, sp, rb + F.cursor, re, can_expand);
+      const bool is_set = c.valid && (c.sub & SET_BIT);
+      const uint32_t node = c.sub & ~SET_BIT;
+      // a set visited before this chunk is a leaf whatever comes first (the visited set only
+      // grows): only unvisited sets with rows are order-dependent candidates, taken one by one.
+      // The visited lookup does not wait for the row range (both depend on the subject only).
       bool cand = false;
-      uint64_t crb = 0, cre = 0;
-      if (valid && can_expand && (sub & SET_BIT)) {
-        const uint32_t c = sub & ~SET_BIT;
-        crb = s.row_off[c];
-        cre = s.row_off[c + 1];
-        cand = cre > crb && !st.contains(c);
+      uint32_t vat = 0;
+      if (is_set && can_expand) {
+        const bool unseen = pol.unseen(node, vat);
+        cand = c.clen > 0 && unseen;
       }
-      const uint32_t mc = sw_bits(__ballot(cand));
-      const uint32_t p = mc ? (uint32_t)(__ffs(mc) - 1) : (uint32_t)SW;
-      const bool leaf = valid && (uint32_t)gl < p;
-      if (!can_expand && !sw_add(st, leaf && (sub & SET_BIT), sub & ~SET_BIT, n_vis)) {
+      const typename G::Mask mc = G::ballot(cand);
+      const uint32_t p = mc ? G::first(mc) : (uint32_t)G::width;
+      // everything before the first candidate: leaves (and marks, order-free for non-candidates)
+      const bool leaf = c.valid && (uint32_t)G::lane() < p;
+      // d-1 <= 1: child sets become leaves but BuildTree still marks them visited, which a later
+      // (shallower) encounter elsewhere in the tree observes.  Sets without rows need no mark:
+      // any encounter of them is a leaf.  SubjectIDs are never marked (engine.go:41-45).
+      if (!can_expand && !pol.mark(leaf && is_set, node)) {
         status = EXP_OVERFLOW;
         break;
       }
-      sw_emit(S, leaf, rec_subject(s, sub));
-      count += (uint32_t)__popc(sw_bits(__ballot(leaf)));
+      emit<G>(S, leaf, pol.leaf_rec(s, c));
+      count += G::count(G::ballot(leaf));
       if (!S.ok) return EXP_ARENA;
-      if (p == (uint32_t)SW) {
-        F.cursor += (uint32_t)min<uint64_t>(SW, re - (rb + F.cursor));
+      if (p == (uint32_t)G::width) {
+        F.cursor += c.width;
         continue;
       }
-      const int src = gb + (int)p;
-      const uint32_t csub = __shfl(sub, src, 64);
-      const uint32_t cnode = csub & ~SET_BIT;
-      const uint32_t clen = (uint32_t)__shfl((uint32_t)(cre - crb), src, 64);
-      const uint64_t cbeg = ((uint64_t)(uint32_t)__shfl((uint32_t)(crb >> 32), src, 64) << 32) |
-                            (uint32_t)__shfl((uint32_t)crb, src, 64);
+      // the candidate at lane p, in order.  It is still unvisited: leaf sets are marked only when
+      // !can_expand and candidates exist only when can_expand, so nothing was inserted since the scan.
+      const uint32_t cnode = G::shfl(node, p), clen = G::shfl(c.clen, p), cat = G::shfl(vat, p);
+      const uint64_t cbeg = G::shfl(c.crb, p);
+      const kg_tree_node u = pol.union_rec(s, c, p, cnode, clen);
       F.cursor += p + 1;
-      const uint32_t before = n_vis;
-      if (!sw_add(st, gl == 0, cnode, n_vis)) {
+      if (!pol.take(cnode, cat)) {
         status = EXP_OVERFLOW;
         break;
       }
-      if (n_vis == before) {  // already visited: BuildTree -> nil -> Leaf{row subject}
-        sw_emit(S, gl == 0, rec_subject(s, csub));
-        count++;
-        if (!S.ok) return EXP_ARENA;
-        continue;
-      }
-      sw_emit(S, gl == 0, rec_set(s, 1, cnode, clen));
+      emit<G>(S, G::lane() == 0, u);
       count++;
       if (!S.ok) return EXP_ARENA;
-      if (sp >= stack_cap) {
+      if (sp >= pol.max_sp) {
         status = EXP_OVERFLOW;
         break;
       }
-      if (gl == 0) stack[sp] = F;
+      pol.push(sp, F);
       sp++;
       F = ExpFrame{cbeg, cnode, 0, clen, F.d - 1};
       pushed = true;
@@ -682,14 +582,15 @@ __device__ int expand_root_sw(const DevSnap& s, const SubStore& st, const kg_set
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
     sp--;
-    F = stack[sp];
+    F = pol.pop(sp);
   }
+  pol.finish();
   n_records = count;
   return status;
 }
 
 // Pass 0: every root, 16 walkers per workgroup; what a walker gives up goes to the p0 list (the 64-lane
-// pass).  Roots are dequeued through ExpCtl::rhead (8 ranges), one walker at a time.
+// pass).  Roots are dequeued through ExpCtl::rhead (claim_ranged), one walker at a time.
 __global__ __launch_bounds__(256) void k_expand_sub(DevSnap s, const kg_set* __restrict__ roots, uint32_t n,
                                                     int32_t global, ExpCtl* ctl, RootOut* outs, kg_tree_node* arena,
                                                     uint32_t* next, uint32_t n_chunks, ExpFrame* stacks,
@@ -698,29 +599,20 @@ __global__ __launch_bounds__(256) void k_expand_sub(DevSnap s, const kg_set* __r
   __shared__ unsigned long long s_recs;
   if (threadIdx.x == 0) s_recs = 0;
   __syncthreads();
-  const int walker = threadIdx.x / SW, gl = sw_lane();
-  const SubStore st{vis_all[walker]};
-  ExpFrame* stack = stacks + ((size_t)blockIdx.x * (256 / SW) + walker) * stack_cap;
+  using G = Lanes<SW>;
+  const int walker = threadIdx.x / SW, gl = G::lane();
+  // PlainChunks{stack, max_sp}, st{vis}, n_vis
+  SubPolicy pol{{stacks + ((size_t)blockIdx.x * (256 / SW) + walker) * stack_cap, (int)stack_cap}, {vis_all[walker]}, 0};
   Stream S{arena, next, n_chunks, ctl, 0, 0, 0, true};
   unsigned long long recs = 0;
-  const uint32_t rper = (n + 7) / 8;
-  uint32_t r_at = blockIdx.x & 7, r_tried = 0;
+  RangeCursor rc = range_cursor();
   for (;;) {
     uint32_t ri = NONE;
-    if (gl == 0)
-      for (; r_tried < 8; r_tried++, r_at = (r_at + 1) & 7) {
-        const uint32_t lo = r_at * rper, hi = min(n, lo + rper);
-        if (lo >= hi || ld_sc1(&ctl->rhead[r_at * 32]) >= hi - lo) continue;
-        const uint32_t k = atomicAdd(&ctl->rhead[r_at * 32], 1u);
-        if (k < hi - lo) {
-          ri = lo + k;
-          break;
-        }
-      }
-    ri = __shfl(ri, sw_base(), 64);
+    if (gl == 0) ri = claim_ranged(ctl->rhead, n, rc);
+    ri = G::shfl(ri, 0);
     if (ri >= n) break;
     uint32_t nr = 0;
-    const int r = expand_root_sw(s, st, roots[ri], global, stack, stack_cap, S, nr);
+    const int r = expand_walk<G>(s, pol, roots[ri], global, S, nr);
     if (gl == 0) {
       if (r == EXP_OVERFLOW) {
         p0_list[atomicAdd(&ctl->p0_count, 1u)] = ri;
@@ -741,34 +633,29 @@ __global__ __launch_bounds__(256) void k_expand_lds(DevSnap s, const kg_set* __r
                                                     uint32_t* next, uint32_t n_chunks, ExpFrame* stacks,
                                                     uint32_t stack_cap, uint32_t* p2_list, int skip,
                                                     const uint32_t* qlist) {
+  // 25.6 KB of LDS a workgroup: 6 workgroups per CU, 6 waves per SIMD.  The kernel's 73 VGPRs allow 6 as
+  // well (7 up to 72): a smaller WaveLds makes the registers the bound
   __shared__ WaveLds lds_all[4];
   const int wave = threadIdx.x >> 6, lane = lane_id();
   LdsStore st{&lds_all[wave]};
-  ExpFrame* stack = stacks + (size_t)(blockIdx.x * 4 + wave) * stack_cap;
+  // PlainChunks{stack, max_sp}, ListedVisits{st, n_vis}
+  LdsPolicy pol{{stacks + (size_t)(blockIdx.x * 4 + wave) * stack_cap, 0x7FFF}, {st, 0}};
   Stream S{arena, next, n_chunks, ctl, 0, 0, 0, true};
   unsigned long long recs = 0;
-  // roots in 8 ranges, each dequeued through its own head (ExpCtl::rhead; with qlist -- pass 0's
-  // overflows, ctl->p0_count of them -- ExpCtl::qhead): this XCD's range first
+  // the roots (ExpCtl::rhead), or with qlist pass 0's overflows, ctl->p0_count of them (ExpCtl::qhead)
   const uint32_t cnt = qlist ? ctl->p0_count : n;
   uint32_t* heads = qlist ? ctl->qhead : ctl->rhead;
-  const uint32_t rper = (cnt + 7) / 8;
-  uint32_t r_at = blockIdx.x & 7, r_tried = 0;
+  RangeCursor rc = range_cursor();
   for (;;) {
     uint32_t ri = NONE;
-    if (lane == 0)
-      for (; r_tried < 8; r_tried++, r_at = (r_at + 1) & 7) {
-        const uint32_t lo = r_at * rper, hi = min(cnt, lo + rper);
-        if (lo >= hi || ld_sc1(&heads[r_at * 32]) >= hi - lo) continue;
-        const uint32_t k = atomicAdd(&heads[r_at * 32], 1u);
-        if (k < hi - lo) {
-          ri = qlist ? qlist[lo + k] : lo + k;
-          break;
-        }
-      }
+    if (lane == 0) {
+      ri = claim_ranged(heads, cnt, rc);
+      if (qlist && ri != NONE) ri = qlist[ri];
+    }
     ri = __shfl(ri, 0, 64);
     if (ri >= n) break;
     uint32_t nr = 0;
-    const int r = skip ? EXP_OVERFLOW : expand_root(s, st, roots[ri], global, stack, S, nr);
+    const int r = skip ? EXP_OVERFLOW : expand_walk<Lanes<64>>(s, pol, roots[ri], global, S, nr);
     if (lane == 0) {
       if (r == EXP_OVERFLOW) {
         p2_list[atomicAdd(&ctl->p2_count, 1u)] = ri;
@@ -793,6 +680,7 @@ __device__ void expand_slot_loop(const DevSnap& s, const kg_set* __restrict__ ro
                                  uint32_t* clear_base, uint64_t clear_words, uint32_t* p3_list) {
   __shared__ ExpLds X;
   const int lane = lane_id();
+  CachedPolicy<Store> pol{{st, 0}, X, stack};  // ListedVisits{st, n_vis}, X, gstack
   Stream S{arena, next, n_chunks, ctl, 0, 0, 0, true};
   unsigned long long recs = 0;
   for (;;) {
@@ -802,9 +690,7 @@ __device__ void expand_slot_loop(const DevSnap& s, const kg_set* __restrict__ ro
     if (k >= count) break;
     const uint32_t ri = qlist[k];
     uint32_t nr = 0;
-    // the walk with LDS-cached frames (round 3; the "expand_tail" knob that kept round 2's walk beside
-    // it was removed in round 6)
-    const int r = expand_root_x(s, st, roots[ri], global, stack, S, nr, X);
+    const int r = expand_walk<Lanes<64>>(s, pol, roots[ri], global, S, nr);
     if (r == EXP_OVERFLOW && p3_list) {
       uint4* b4 = reinterpret_cast<uint4*>(clear_base);  // clear_words: multiple of 4, 16-B aligned
       for (uint64_t i = lane; i < clear_words / 4; i += 64) b4[i] = make_uint4(0, 0, 0, 0);
@@ -858,11 +744,17 @@ __global__ __launch_bounds__(64) void k_expand_hbm(DevSnap s, const kg_set* __re
 //   * a level's entries are one contiguous range (rows are allocated by a bump counter while the
 //     level before runs), so the next level is edge-parallel over that range: a run-head mark per
 //     row start and the head of each 64-entry tile find an entry's source row position;
-//   * the walk (one wave) is expand_root_x's order over the copy: one trip per chunk (the slot's
+//   * the walk (one wave) is expand_walk's order over the copy: one trip per chunk (the slot's
 //     recently written lines, L2 / MALL) and the visited set is an LDS bitmap over local ids.
-// The output is identical to expand_root's (same candidates in the same order).  A root that outgrows
+// The output is identical to expand_walk's (same candidates in the same order).  A root that outgrows
 // a slot (entries, local ids, map probes) goes on to the next pass: small slots -> large slots ->
 // the hash pass (expand_slot_loop) -> the whole-graph bitmap pass.
+//
+// This walk is NOT an expand_walk policy, on purpose.  It is most of a C5 call's kernel time and its
+// step is bound by its own instruction chain, and it has three things no other
+// walker has: children at rest depth 1 are expanded inline from registers, a pushed child's first chunk
+// is prefetched, and records are staged in LDS.  Hooks for those in the skeleton would be machinery
+// used once.  It shares the small pieces only: clamp_depth, rec_set, alloc_chunk, the status codes.
 struct GwEnt {
   uint32_t sub;   // the row subject as stored (SET_BIT | node, or a subject id)
   uint32_t loc;   // the child set's local id (a set with rows), else NONE; during the gather: its map slot
@@ -1013,8 +905,7 @@ __global__ __launch_bounds__(256) void k_expand_gw(DevSnap s, const kg_set* __re
     if (!s_src) break;
     const uint32_t ri = s_ri;
     const kg_set root = roots[ri];
-    int32_t d0 = root.max_depth;
-    if (d0 <= 0 || global < d0) d0 = global;  // engine.go:37-39
+    const int32_t d0 = clamp_depth(root.max_depth, global);  // engine.go:37-39
     const uint32_t rn = root.sns == KG_SUBJECT_ID ? NONE : nmap_find(s, root.sns, root.srel, root.sobj);
     const uint64_t rb0 = rn == NONE ? 0 : s.row_off[rn];
     const uint64_t len0 = rn == NONE ? 0 : s.row_off[rn + 1] - rb0;
@@ -1125,18 +1016,9 @@ __global__ __launch_bounds__(256) void k_expand_gw(DevSnap s, const kg_set* __re
       kg_tree_node* sbuf = reinterpret_cast<kg_tree_node*>(s_out);
       // staged -> a new arena chunk (linked after the root's previous one); n records, n <= CHUNK
       auto flush = [&](uint32_t n) {
-        uint32_t c = 0;
-        if (lane == 0) c = claim_chunk(ctl, S.n_chunks);
-        c = __shfl(c, 0, 64);
-        if (c >= S.n_chunks) {
-          if (lane == 0) ctl->overflow = 1;
-          S.ok = false;
-          return;
-        }
-        if (lane == 0) {
-          S.next[c] = NONE;
-          if (S.cur != NONE) S.next[S.cur] = c;
-        }
+        const uint32_t c = alloc_chunk<Lanes<64>>(S);
+        if (!S.ok) return;
+        if (lane == 0 && S.cur != NONE) S.next[S.cur] = c;
         if (S.first == NONE) S.first = c;
         S.cur = c;
         uint4* dst = reinterpret_cast<uint4*>(S.arena + (size_t)c * CHUNK);
@@ -1176,7 +1058,7 @@ __global__ __launch_bounds__(256) void k_expand_gw(DevSnap s, const kg_set* __re
           bool pushed = false;
           while (eb + F.cursor < ee) {
             const uint64_t at0 = eb + F.cursor;
-            // (caching each frame level's chunk in LDS, as expand_root_x does, measured slower here: the
+            // (caching each frame level's chunk in LDS, as CachedPolicy does, measured slower here: the
             // walk is bound by its own instruction chain, ~1 us per chunk, not by the copy's latency)
             const uint32_t width = (uint32_t)min<uint64_t>(64, ee - at0);
             const bool valid = (uint32_t)lane < width;
@@ -1396,6 +1278,7 @@ struct ExpandBufs {
   // arena rerun or an error can leave keys behind; a completed call leaves them clear -- every root's
   // walk removes its keys, an overflowing one zeroes its table)
   bool bm_dirty = true;
+  uint64_t bm_cap2 = 0;  // the pass-2 list capacity B.bm was last laid out for
   DevBuf<kg_tree_node> arena;
   DevBuf<uint32_t> next;
   uint32_t chunks = 0;
@@ -1528,7 +1411,7 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
   const uint64_t nn = std::max<uint32_t>(s->ds.n_nodes, 1), words = ((nn + 31) / 32 + 1 + 3) & ~3ull;
   // pass 2: 2 slots per CU, each a visited hash + list of up to 256 Ki nodes (~5 MB a slot, <= 2 GiB;
   // 4 per CU measured the same on C5)
-  const uint64_t cap2 = (std::min<uint64_t>(nn, 1ull << 18) + 3) & ~3ull;
+  const uint64_t cap2 = (std::min<uint64_t>(nn, s->expand_hash_cap) + 3) & ~3ull;
   uint64_t tsize = 64;
   while (tsize < 2 * cap2 + 128) tsize <<= 1;
   const uint32_t slots2 =
@@ -1562,7 +1445,8 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     const uint32_t* bm0 = B.bm;
     if (!rc && (e = grow(B.bm, clear_words + (size_t)slots2 * cap2 + nn)) != hipSuccess)
       fail("hipMalloc", e);
-    if (B.bm != bm0) B.bm_dirty = true;
+    if (B.bm != bm0 || B.bm_cap2 != cap2) B.bm_dirty = true;  // (expand_hash_cap moves the tables over old lists)
+    B.bm_cap2 = cap2;
   }
   for (auto& x : B.ev)
     if (!rc && !x && (e = hipEventCreate(&x)) != hipSuccess) fail("hipEventCreate", e);
@@ -1644,6 +1528,30 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     n_chunks *= 4;  // grow the arena and rerun (outputs are rewritten from scratch)
   }
   B.bm_dirty = rc != 0 || h.overflow != 0;  // only a completed call leaves the tables clear
+  // what the device-output and the host-output tail below share: the compaction launch between its
+  // events, and the call's end (kernel time, or on failure the clean-up after `release` gave the
+  // output's buffers back)
+  auto compact = [&](const uint64_t* off, kg_tree_node* dst) {
+    (void)hipEventRecord(B.ev[2], stream);
+    hipLaunchKernelGGL(k_expand_compact, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, stream, B.outs, (uint32_t)n, off,
+                       B.arena, B.next, dst);
+    (void)hipEventRecord(B.ev[3], stream);
+    return hipGetLastError();
+  };
+  auto finish = [&](uint64_t total, auto release) {
+    out->n_nodes = total;
+    if (!rc) {
+      float a = 0, b = 0;
+      (void)hipEventElapsedTime(&a, B.ev[0], B.ev[1]);
+      if (total) (void)hipEventElapsedTime(&b, B.ev[2], B.ev[3]);
+      out->kernel_ms = (double)a + (double)b;
+      return 0;
+    }
+    B.bm_dirty = true;
+    release(total * sizeof(kg_tree_node));
+    memset(out, 0, sizeof *out);
+    return rc;
+  };
   if (dev_io) {
     // offsets by a device scan of the roots' counts; the total and the overflow tally come back in one
     // readback, then the records are compacted into the output (no host pass over the roots)
@@ -1671,26 +1579,12 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
       out->nodes = (kg_tree_node*)tree_dev_get(s->device, total * sizeof(kg_tree_node));
       if (!out->nodes) rc = set_error(-4, "device allocation failed");
     }
-    if (!rc && total) {
-      (void)hipEventRecord(B.ev[2], stream);
-      hipLaunchKernelGGL(k_expand_compact, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, stream, B.outs, (uint32_t)n,
-                         out->root_off, B.arena, B.next, out->nodes);
-      (void)hipEventRecord(B.ev[3], stream);
-      if ((e = hipGetLastError()) != hipSuccess || (e = B.wait(stream)) != hipSuccess) fail("compact", e);
-    }
-    out->n_nodes = total;
-    if (!rc) {
-      float a = 0, b = 0;
-      (void)hipEventElapsedTime(&a, B.ev[0], B.ev[1]);
-      if (total) (void)hipEventElapsedTime(&b, B.ev[2], B.ev[3]);
-      out->kernel_ms = (double)a + (double)b;
-    } else {
-      B.bm_dirty = true;
-      tree_dev_put(s->device, out->nodes, total * sizeof(kg_tree_node));
+    if (!rc && total && ((e = compact(out->root_off, out->nodes)) != hipSuccess || (e = B.wait(stream)) != hipSuccess))
+      fail("compact", e);
+    return finish(total, [&](size_t bytes) {
+      tree_dev_put(s->device, out->nodes, bytes);
       tree_dev_put(s->device, out->root_off, (n + 1) * 8);
-      memset(out, 0, sizeof *out);
-    }
-    return rc;
+    });
   }
   std::vector<RootOut> ho(n);
   if (!rc && (e = hipMemcpyAsync(ho.data(), B.outs, n * sizeof(RootOut), hipMemcpyDeviceToHost, stream)) != hipSuccess)
@@ -1718,31 +1612,16 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
     if (!rc && (e = grow(B.d_off, n + 1)) != hipSuccess) fail("hipMalloc", e);
     if (!rc && (e = hipMemcpyAsync(B.d_off, out->root_off, (n + 1) * 8, hipMemcpyHostToDevice, stream)) != hipSuccess)
       fail("H2D", e);
-    if (!rc) {
-      (void)hipEventRecord(B.ev[2], stream);
-      hipLaunchKernelGGL(k_expand_compact, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, stream, B.outs, (uint32_t)n,
-                         B.d_off, B.arena, B.next, B.dst);
-      (void)hipEventRecord(B.ev[3], stream);
-      if ((e = hipMemcpyAsync(out->nodes, B.dst, total * sizeof(kg_tree_node), hipMemcpyDeviceToHost, stream)) !=
-              hipSuccess ||
-          (e = B.wait(stream)) != hipSuccess)
-        fail("compact", e);
-    }
+    if (!rc && ((e = compact(B.d_off, B.dst)) != hipSuccess ||
+                (e = hipMemcpyAsync(out->nodes, B.dst, total * sizeof(kg_tree_node), hipMemcpyDeviceToHost, stream)) !=
+                    hipSuccess ||
+                (e = B.wait(stream)) != hipSuccess))
+      fail("compact", e);
   }
-  out->n_nodes = total;
-  if (!rc) {
-    float a = 0, b = 0;
-    (void)hipEventElapsedTime(&a, B.ev[0], B.ev[1]);
-    if (total) (void)hipEventElapsedTime(&b, B.ev[2], B.ev[3]);
-    out->kernel_ms = (double)a + (double)b;
-  }
-  if (rc) {
-    B.bm_dirty = true;
-    if (out->pinned) tree_pool_put(out->nodes, total * sizeof(kg_tree_node));
+  return finish(total, [&](size_t bytes) {
+    if (out->pinned) tree_pool_put(out->nodes, bytes);
     free(out->root_off);
-    memset(out, 0, sizeof *out);
-  }
-  return rc;
+  });
 }
 
 }  // namespace kg

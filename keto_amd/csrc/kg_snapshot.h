@@ -325,6 +325,7 @@ struct Snapshot {
   // 16-lane walkers (pass 0) are skipped and the 64-lane pass takes every root
   int expand_gw = 1;
   int expand_skip_lds = 0;
+  uint32_t expand_hash_cap = 1u << 18;  // "expand_hash_cap" (tests): visited sets per hash-pass slot; small values reach the bitmap pass
   // kg_snapshot_tune("level_events"): batches with stats time every tail-tier level launch with a HIP
   // event pair (kg_stats tail_ms); off by default -- the records leave gaps between the launches
   int level_events = 0;

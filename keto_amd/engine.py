@@ -189,10 +189,10 @@ class Snapshot:
 
     def tune(self, key: str, value: int) -> None:
         """Engine knobs (kg_snapshot_tune; keto_amd/csrc/kg_abi.cpp tune_one lists them with their ranges;
-        29 since round 6 removed the ones that measured flat): tier chain -- back_wgs, back_edges, stream_ecap,
+        29 since round 6 removed the ones that measured flat, 30 with expand_hash_cap): tier chain -- back_wgs, back_edges, stream_ecap,
         stream_wgs, stream_steal, grid_wgs, grid_cap, grid_reserve, grid_ms, grid_ms_words, grid_ms_bytes,
         grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests); expand -- expand_gw, expand_gw_wait_us,
-        expand_skip_lds (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
+        expand_skip_lds (tests), expand_hash_cap (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
         shard_max_bytes, shard_force_overflow (tests), shard_bucket, shard_vis, shard_heavy, shard_budget,
         shard_back_budget, shard_remote_meta (read at the first binding).  Build-time, from the environment:
         KG_ADJX_ORDER=0 lays adjx out in node order instead of hot-first."""

@@ -44,9 +44,8 @@ def _records(rec):
 GW_MODES = [(1, 0), (1, 1), (0, 1), (1, 2)]
 
 
-@pytest.mark.parametrize("gw,skip", GW_MODES, ids=["default", "gw-all", "hash-all", "lds64-all"])
-@pytest.mark.parametrize("seed", range(5))
-def test_random_expand_vs_oracle(seed, gw, skip):
+def _random_graph(seed):
+    """(registry, oracle, roots) of test_random_expand_vs_oracle's seeded graph"""
     rng = np.random.default_rng(50 + seed)
     n_obj = 30 + 30 * seed
     tuples = []
@@ -59,8 +58,6 @@ def test_random_expand_vs_oracle(seed, gw, skip):
             s = f"u{rng.integers(30)}"
         tuples.append(RelationTuple.from_string(f"{ns}:{obj}#{rel}@{s}"))
     reg = Registry(tuples, [])
-    reg.snapshot.tune("expand_gw", gw)
-    reg.snapshot.tune("expand_skip_lds", skip)
     it = reg.interner
     oracle = Oracle(it.tuples_array(tuples), it.wildcard_rel)
     roots = []
@@ -70,25 +67,44 @@ def test_random_expand_vs_oracle(seed, gw, skip):
         else:
             roots.append([it.ns_id(rng.choice(["a", "b"])), it.obj_id(f"o{rng.integers(n_obj + 2)}"),
                           it.rel_id(rng.choice(["r0", "r1", "r2"])), int(rng.integers(-1, 7))])
+    return reg, oracle, roots
+
+
+def _root_rows(roots):
+    arr = np.asarray(roots, np.int64)
+    arr[:, 3] = arr[:, 3].astype(np.int32).view(np.uint32)
+    return arr.astype(np.uint32)
+
+
+@pytest.mark.parametrize("gw,skip", GW_MODES, ids=["default", "gw-all", "hash-all", "lds64-all"])
+@pytest.mark.parametrize("seed", range(5))
+def test_random_expand_vs_oracle(seed, gw, skip):
+    reg, oracle, roots = _random_graph(seed)
+    reg.snapshot.tune("expand_gw", gw)
+    reg.snapshot.tune("expand_skip_lds", skip)
     for gmax in (1, 2, 4, 7):
         ex = ExpandEngine(reg.snapshot)
         ex.config.max_read_depth = gmax
-        arr = np.asarray(roots, np.int64)
-        arr[:, 3] = arr[:, 3].astype(np.int32).view(np.uint32)
-        got = ex.build_trees_ids(arr.astype(np.uint32))
+        got = ex.build_trees_ids(_root_rows(roots))
         for r, g in zip(roots, got):
             exp = oracle.expand(r[0], r[1], r[2], r[3], gmax)
             _cmp_records(exp, g, (r, gmax))
+
+
+def _wide_rows_graph():
+    """900 + 300 sets under one root, rows wider than a wave"""
+    tuples = [RelationTuple.from_string(f"g:root#m@(g:c{i}#m)") for i in range(900)]
+    tuples += [RelationTuple.from_string(f"g:c{i}#m@(g:d{i % 300}#m)") for i in range(900)]
+    tuples += [RelationTuple.from_string(f"g:d{i}#m@u{i}") for i in range(300)]
+    tuples += [RelationTuple.from_string(f"g:c{i}#m@x{i}") for i in range(0, 900, 7)]
+    return tuples
 
 
 @pytest.mark.parametrize("gw", [1, 0])
 def test_expand_overflow_tier_and_wide_rows(gw):
     # a root whose visited set exceeds the LDS tier (pass 2: gather-walk or the HBM hash) and rows wider
     # than a wave
-    tuples = [RelationTuple.from_string(f"g:root#m@(g:c{i}#m)") for i in range(900)]
-    tuples += [RelationTuple.from_string(f"g:c{i}#m@(g:d{i % 300}#m)") for i in range(900)]
-    tuples += [RelationTuple.from_string(f"g:d{i}#m@u{i}") for i in range(300)]
-    tuples += [RelationTuple.from_string(f"g:c{i}#m@x{i}") for i in range(0, 900, 7)]
+    tuples = _wide_rows_graph()
     reg = Registry(tuples, [])
     reg.snapshot.tune("expand_gw", gw)
     it = reg.interner
@@ -99,6 +115,84 @@ def test_expand_overflow_tier_and_wide_rows(gw):
         got = ex.build_tree(SubjectSet("g", "root", "m"), 0)
         exp = oracle_tree(oracle.expand(it.ns_id("g"), it.obj_id("root"), it.rel_id("m"), 0, gmax), it)
         assert got == exp, gmax
+
+
+HASH_CAP_DEFAULT = 1 << 18
+
+
+def _marked_sets(oracle, exp, rows):
+    """Sets BuildTree marks visited for the tree `exp` (oracle records): every set with rows is marked
+    when it first appears, as a union or as a leaf.  rows caches which sets have rows."""
+    if exp is None:
+        return 0
+    seen = set()
+    for r in np.asarray(exp, np.int64):
+        key = (int(r[2]), int(r[3]), int(r[4]))
+        if not r[1] or key in seen:
+            continue
+        if key not in rows:
+            rows[key] = oracle.expand(key[0], key[1], key[2], 0, 1) is not None
+        if rows[key]:
+            seen.add(key)
+    return len(seen)
+
+
+def _bitmap_pass_calls(snap, oracle, rows, gmax, caps=(16,)):
+    """Expands `rows` (kg_set rows) at depth gmax with hash-pass lists of `caps` entries -- every root that
+    marks more sets than that is answered by the whole-graph bitmap pass -- TWICE in a row, then twice at
+    the default list size, all on one engine.  The library clears the visited tables and the bitmap when
+    the list size changes (their layout moves), so it is the second call at each size that starts from
+    what the call before left behind: a bit or a key that pass 3 or an overflowing hash slot does not
+    remove shows there as a set wrongly taken for visited.  Every call must equal the oracle, so the
+    small-list calls and the default calls give identical records.  Returns the largest number of sets a
+    root marks (from the oracle's tree)."""
+    ex = ExpandEngine(snap)
+    ex.config.max_read_depth = gmax
+    exp = [oracle.expand(int(r[0]), int(r[1]), int(r[2]), int(d), gmax)
+           for r, d in zip(rows, rows[:, 3].astype(np.int32))]
+    for cap in caps:
+        calls = []
+        for size in (cap, cap, HASH_CAP_DEFAULT, HASH_CAP_DEFAULT):
+            snap.tune("expand_hash_cap", size)
+            calls.append((size, ex.build_trees_ids(rows)))
+        for k, (size, got) in enumerate(calls):
+            for r, e, g in zip(rows, exp, got):
+                _cmp_records(e, g, (r.tolist(), gmax, "list size", size, "call", k))
+    has_rows = {}
+    return max(_marked_sets(oracle, e, has_rows) for e in exp)
+
+
+def test_expand_bitmap_pass_wide_rows():
+    """Pass 3 (k_expand_hbm, the whole-graph bitmap): the wide-rows root outgrows the LDS store (512),
+    then a 16-entry hash-pass list (expand_hash_cap), and is answered by the bitmap pass."""
+    tuples = _wide_rows_graph()
+    reg = Registry(tuples, [])
+    reg.snapshot.tune("expand_gw", 0)
+    it = reg.interner
+    oracle = Oracle(it.tuples_array(tuples), it.wildcard_rel)
+    root = np.asarray([[it.ns_id("g"), it.obj_id("root"), it.rel_id("m"), 0]], np.uint32)
+    for gmax in (2, 3, 4):
+        assert _bitmap_pass_calls(reg.snapshot, oracle, root, gmax) > 512, gmax
+
+
+@pytest.mark.parametrize("seed", [1, 4])
+def test_expand_bitmap_pass_random(seed):
+    """Pass 3 on the random graphs: no LDS pass, no gather-walk, small hash-pass lists, so every root that
+    marks more sets than a list holds is answered by the bitmap pass.
+
+    These graphs are sparse: counted from the oracle's trees, the most sets with rows one root marks is
+    4 / 7 / 9 (seed 1) and 4 / 11 / 14 (seed 4) at depths 2 / 4 / 7 -- never more than 16, so by that count
+    the calls with 16-entry lists do not reach pass 3 on these graphs (they are kept: same trees).  Next to
+    them the test runs 4-entry lists (the key's lower bound), and for those it asserts at depths 4 and 7
+    that some root outgrows the list; at depth 2 none does."""
+    reg, oracle, roots = _random_graph(seed)
+    reg.snapshot.tune("expand_gw", 0)
+    reg.snapshot.tune("expand_skip_lds", 1)
+    rows = _root_rows(roots)
+    for gmax in (2, 4, 7):
+        most = _bitmap_pass_calls(reg.snapshot, oracle, rows, gmax, caps=(16, 4))
+        print(f"seed {seed} depth {gmax}: a root marks up to {most} sets with rows")
+        assert gmax == 2 or most > 4, gmax
 
 
 def test_expand_gather_walk_large_slot_and_cycles():
