@@ -671,6 +671,62 @@ typedef struct {
 int kg_lookup_subjects(kg_snapshot* s, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
                        kg_lookup_buf* out);
 
+/* ---- tuple listing ----------------------------------------------------------------------- */
+/* GetRelationTuples (GET /relation-tuples, ReadService.ListRelationTuples; relationtuple.Manager over a
+ * RelationQuery, internal/persistence/sql/relationtuples.go:124-145,203-244) on the device snapshot:
+ * every field of the query is optional, rows come back in order-key order, keyset paged.  n requests
+ * per call; request i owns rows[req_off[i] .. req_off[i+1]) and keys[...] likewise.
+ * Match: the row's namespace, object and relation are compared for the fields named in mask (0: every
+ * row).  With KG_Q_SUBJECT, t.sns == KG_SUBJECT_ID matches only subject-id rows with the id t.sobj, and
+ * anything else matches only subject-set rows with exactly the set (t.sns, t.sobj, t.srel) -- `...` sets
+ * are rows like any other (whereSubject, :124-145).  The fields of t not named in mask are ignored.  An id
+ * that occurs in no row (or fits no node) is not an error: the page is empty.  Raw tuples only, exactly as
+ * kg_snapshot_rows: a materialised union node's merged check rows are never returned.
+ * Order key: the key kg_snapshot_create_ordered / kg_snapshot_apply gave the row (the persister's shard
+ * ids); on a snapshot without keys (kg_snapshot_create, synthetic) position + 1 in kg_snapshot_export's
+ * order.  Keys are expected to be distinct, as shard ids are; rows with equal keys come in
+ * kg_snapshot_export's order, and a page that ends inside a run of equal keys skips the rest of the run
+ * (`after` is exclusive), as SQL keyset paging on a non-unique column does.
+ * Page: the `limit` rows with the smallest keys above `after`, ascending.  matched[i] counts every row
+ * that matches with key > after; next[i] is the key of the last returned row when matched[i] > limit
+ * (pass it as the next call's `after`), else 0 -- the reference's LIMIT per_page + 1 (:215,:230).
+ * Failures: limit == 0 is -2.  A hash-sharded snapshot returns its own rank's rows, as kg_snapshot_rows;
+ * merging the ranks' pages is the caller's.
+ * Cost: a query with namespace, object and relation reads that node's row from the first key above
+ * `after`; one with some of them reads every node's triple and then the matching nodes' rows; one with
+ * none reads every row entry (4 B each, 8 B more for the key of those whose subject matches).  Matches
+ * that fit a list of max("query_cap", min(limit, entries)) pairs are sorted directly (one scan); more are
+ * first narrowed by histogram passes over 11 key bits each (two more scans for uniform or dense keys).
+ * The call never allocates in proportion to the rows or the matches.  rows_scanned / passes: row entries
+ * tested, summed over the scans / scans, per call.  kg_snapshot_tune key "query_cap": entries of that list
+ * (0 = default 2^20; small values force the narrowing in tests).
+ * Thread-safe (a lane set per call, one replica, rotated).  The output arrays are one block of
+ * library-allocated pinned memory, returned by kg_query_free. */
+#define KG_Q_NS 1u
+#define KG_Q_OBJ 2u
+#define KG_Q_REL 4u
+#define KG_Q_SUBJECT 8u
+typedef struct {
+  uint32_t mask;    /* KG_Q_*: which fields of t are set; 0 = every row            */
+  kg_tuple t;       /* with KG_Q_SUBJECT: (sns,sobj,srel), or sns = KG_SUBJECT_ID   */
+  uint64_t after;   /* only rows with order key > after (0: from the start)        */
+  uint32_t limit;   /* rows to return at most (>= 1)                               */
+} kg_row_query;
+typedef struct {
+  uint64_t* req_off;  /* n_reqs + 1 */
+  kg_tuple* rows;     /* request i: rows[req_off[i] .. req_off[i+1]), ascending key  */
+  uint64_t* keys;     /* the order key of each returned row                          */
+  uint64_t* next;     /* per request: key of its last returned row when more rows
+                         match beyond it (the next call's `after`), else 0           */
+  uint64_t* matched;  /* per request: rows that match with key > after               */
+  uint64_t n_reqs, n_rows;
+  uint64_t rows_scanned, passes;  /* per call: row entries tested (summed over passes) / scan passes */
+  double kernel_ms;   /* device time of the call (HIP events) */
+  uint64_t pinned;    /* library use */
+} kg_query_buf;
+int kg_snapshot_query(kg_snapshot* s, const kg_row_query* reqs, size_t n, kg_query_buf* out);
+void kg_query_free(kg_query_buf* out);
+
 /* ---- errors ----------------------------------------------------------------------------- */
 /* Thread-local text of the last failing call; returns its length. */
 size_t kg_last_error(char* buf, size_t len);

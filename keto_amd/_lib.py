@@ -107,6 +107,26 @@ class kg_lookup_buf(C.Structure):
                 ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
 
 
+KG_Q_NS, KG_Q_OBJ, KG_Q_REL, KG_Q_SUBJECT = 1, 2, 4, 8
+
+
+class kg_row_query(C.Structure):
+    _fields_ = [("mask", C.c_uint32), ("t", kg_tuple), ("after", C.c_uint64), ("limit", C.c_uint32)]
+
+
+class kg_query_buf(C.Structure):
+    _fields_ = [("req_off", C.POINTER(C.c_uint64)), ("rows", C.POINTER(kg_tuple)), ("keys", C.POINTER(C.c_uint64)),
+                ("next", C.POINTER(C.c_uint64)), ("matched", C.POINTER(C.c_uint64)),
+                ("n_reqs", C.c_uint64), ("n_rows", C.c_uint64), ("rows_scanned", C.c_uint64), ("passes", C.c_uint64),
+                ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
+
+
+# kg_row_query as a numpy record (48 B: the u64 is 8-aligned)
+ROW_QUERY_DTYPE = np.dtype({"names": ["mask", "t", "after", "limit"],
+                            "formats": ["<u4", ("<u4", (6,)), "<u8", "<u4"],
+                            "offsets": [0, 4, 32, 40], "itemsize": 48})
+
+
 class kg_synth_params(C.Structure):
     _fields_ = [("n_tuples_target", C.c_uint64), ("seed", C.c_uint64), ("n_layers", C.c_uint32),
                 ("max_degree", C.c_uint32), ("set_fraction", C.c_float), ("doc_set_fraction", C.c_float),
@@ -124,7 +144,7 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_held_words", "kg_shard_held", "kg_shard_result_slots", "kg_shard_bad_nodes", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats", "kg_batcher_reset_stats", "kg_batcher_destroy",
            "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
            "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
-           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free"]
+           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -204,6 +224,10 @@ def load(path: str = LIB_PATH):
     L.kg_lookup_subjects.restype = C.c_int
     L.kg_lookup_free.argtypes = [C.POINTER(kg_lookup_buf)]
     L.kg_lookup_free.restype = None
+    L.kg_snapshot_query.argtypes = [vp, vp, sz, C.POINTER(kg_query_buf)]
+    L.kg_snapshot_query.restype = C.c_int
+    L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]
+    L.kg_query_free.restype = None
     L.kg_tree_free.argtypes = [C.POINTER(kg_tree_buf)]
     L.kg_tree_free.restype = None
     L.kg_last_error.argtypes = [C.c_char_p, sz]

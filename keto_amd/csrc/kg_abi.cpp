@@ -567,6 +567,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     s->lookup_domain_rows = (int)value;
     return 0;
   }
+  if (strcmp(key, "query_cap") == 0) {
+    if (value < 0 || value > (1ll << 32)) return set_error(-2, "query_cap must be in [0, 2^32]");
+    s->query_cap = (uint64_t)value;
+    return 0;
+  }
   if (strcmp(key, "back_edges") == 0) {
     if (value < 0 || value > (1 << 20)) return set_error(-2, "back_edges must be in [0, 2^20]");
     s->back_edges = (uint32_t)value;
@@ -1000,15 +1005,17 @@ int kg_expand_batch_device(kg_snapshot* sp, const kg_set* d_roots, size_t n, int
   KG_GUARD_END
 }
 
-// One lane of one replica (rotated over the replicas): the walk's masks are per device, and a lookup is
-// one small batch of requests, not a stream of them.  run(replica, lane): the lookup itself.
-static int lookup_call(const char* name, kg_snapshot* sp, const void* reqs, size_t n, kg_lookup_buf* out,
+// One lane of one replica (rotated over the replicas): the walk's masks are per device, and a lookup (or
+// a tuple listing: Buf = kg_query_buf) is one small batch of requests, not a stream of them.
+// run(replica, lane): the call itself.  sharded_ok: a hash-sharded snapshot answers from its own rows.
+extern "C++" template <class Buf>
+static int lookup_call(const char* name, kg_snapshot* sp, const void* reqs, size_t n, Buf* out, bool sharded_ok,
                        const std::function<int(Snapshot*, kg::Lane*)>& run) {
   if (!sp || !out) return set_error(-2, "NULL argument");
   if (n && !reqs) return set_error(-2, "reqs is NULL");
   memset(out, 0, sizeof *out);
   Snapshot* s = reinterpret_cast<Snapshot*>(sp);
-  if (s->shard_n > 1 || kg::shard_comm_of(s, nullptr))
+  if (!sharded_ok && (s->shard_n > 1 || kg::shard_comm_of(s, nullptr)))
     return set_error(-3, "%s: not supported on hash-sharded snapshots", name);
   if (n == 0) {
     out->req_off = (uint64_t*)calloc(1, 8);
@@ -1025,7 +1032,7 @@ static int lookup_call(const char* name, kg_snapshot* sp, const void* reqs, size
 
 int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out) {
   KG_GUARD_BEGIN
-  return lookup_call("kg_lookup_objects", sp, reqs, n, out, [&](Snapshot* rep, kg::Lane* L) {
+  return lookup_call("kg_lookup_objects", sp, reqs, n, out, false, [&](Snapshot* rep, kg::Lane* L) {
     return kg::lookup_objects(rep, L, reqs, n, global_max_depth, out);
   });
   KG_GUARD_END
@@ -1034,7 +1041,7 @@ int kg_lookup_objects(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t 
 int kg_lookup_subjects(kg_snapshot* sp, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
                        kg_lookup_buf* out) {
   KG_GUARD_BEGIN
-  return lookup_call("kg_lookup_subjects", sp, reqs, n, out, [&](Snapshot* rep, kg::Lane* L) {
+  return lookup_call("kg_lookup_subjects", sp, reqs, n, out, false, [&](Snapshot* rep, kg::Lane* L) {
     return kg::lookup_subjects(rep, L, reqs, n, global_max_depth, out);
   });
   KG_GUARD_END
@@ -1042,6 +1049,18 @@ int kg_lookup_subjects(kg_snapshot* sp, const kg_lookup_subj* reqs, size_t n, in
 
 void kg_lookup_free(kg_lookup_buf* out) {
   if (out) kg::lookup_free(out);
+}
+
+// A hash-sharded snapshot lists its own rank's rows, as kg_snapshot_rows.
+int kg_snapshot_query(kg_snapshot* sp, const kg_row_query* reqs, size_t n, kg_query_buf* out) {
+  KG_GUARD_BEGIN
+  return lookup_call("kg_snapshot_query", sp, reqs, n, out, true,
+                     [&](Snapshot* rep, kg::Lane* L) { return kg::query_rows(rep, L, reqs, n, out); });
+  KG_GUARD_END
+}
+
+void kg_query_free(kg_query_buf* out) {
+  if (out) kg::query_free(out);
 }
 
 void kg_tree_free(kg_tree_buf* t) {

@@ -247,6 +247,7 @@ struct Lane {
   size_t cap = 0;  // queries the six above hold
   void* exp = nullptr;  // expand buffers of this lane (kg_expand.hip)
   void* lk = nullptr;   // lookup buffers of this lane (kg_lookup.hip)
+  void* qr = nullptr;   // tuple-listing buffers of this lane (kg_query.hip)
   // kg_check_batch_packed: packed queries on the device (staged through h_q) and the error list
   DevBuf<kg_query_packed> d_pk;
   DevBuf<uint32_t> d_el;  // count word, pad, then (index, code) pairs: room for every query of the chunk
@@ -356,6 +357,7 @@ struct Snapshot {
   // kg_snapshot_tune("lookup_domain_rows") (tests): 1 = kg_lookup_subjects lists its domain from the check
   // rows even where the holder bitmap exists (what a snapshot without reverse indexes does)
   int lookup_domain_rows = 0;
+  uint64_t query_cap = 0;  // kg_snapshot_tune("query_cap"): (key, position) pairs a listing sorts directly (0 = 1 Mi; tests)
   uint64_t grid_ms_cap = 0;  // kg_snapshot_tune("grid_ms_cap"): MS-BFS entries per level buffer (0 = 16 Mi; tests)
   // replicas: the same snapshot on more devices (kg_snapshot_create's device mask); this object is
   // replica 0 and owns the others.  Host-buffer batches and expands are split over all of them.
@@ -480,6 +482,10 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
                     kg_lookup_buf* out);
 void lookup_free(kg_lookup_buf* out);
 void lookup_bufs_free(void* bufs);
+// kg_query.hip: kg_snapshot_query on lane L (the caller holds L->w->mu); query_free returns its output
+int query_rows(Snapshot* s, Lane* L, const kg_row_query* reqs, size_t n, kg_query_buf* out);
+void query_free(kg_query_buf* out);
+void query_bufs_free(void* bufs);
 constexpr uint64_t KG_TREE_DEVICE = 0x100;  // kg_tree_buf.pinned: device-resident trees (low byte: the device)
 void* tree_dev_get(int device, size_t bytes);  // device memory for device-resident tree outputs
 void tree_dev_put(int device, void* p, size_t bytes);

@@ -340,6 +340,7 @@ Lane::~Lane() {
   if (device >= 0) (void)hipSetDevice(device);
   if (exp) expand_bufs_free(exp);
   if (lk) lookup_bufs_free(lk);
+  if (qr) query_bufs_free(qr);
   // the stream's workspace belongs to the replica (freed with it); the stream itself is ours -- synchronised
   // here, where the frees used to do it, because the buffers are released after this body
   if (stream) {

@@ -191,7 +191,7 @@ class Snapshot:
         """Engine knobs (kg_snapshot_tune; keto_amd/csrc/kg_abi.cpp tune_one lists them with their ranges;
         29 since round 6 removed the ones that measured flat, 30 with expand_hash_cap): tier chain -- back_wgs, back_edges, stream_ecap,
         stream_wgs, stream_steal, grid_wgs, grid_cap, grid_reserve, grid_ms, grid_ms_words, grid_ms_bytes,
-        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests); expand -- expand_gw, expand_gw_wait_us,
+        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests); listing -- query_cap; expand -- expand_gw, expand_gw_wait_us,
         expand_skip_lds (tests), expand_hash_cap (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
         shard_max_bytes, shard_force_overflow (tests), shard_bucket, shard_vis, shard_heavy, shard_budget,
         shard_back_budget, shard_remote_meta (read at the first binding).  Build-time, from the environment:
@@ -234,6 +234,32 @@ class Snapshot:
                 raise _lib.KetoGPUError(_lib.last_error())
         return off.astype(np.int64), out[:n]
 
+    def query(self, reqs: np.ndarray, with_stats: bool = False):
+        """GetRelationTuples on the device snapshot (kg_snapshot_query).  reqs: kg_row_query records
+        (_lib.ROW_QUERY_DTYPE; row_queries() builds them).  Returns (rows (m,6) uint32, keys u64 [m],
+        req_off u64 [n+1], next u64 [n], matched u64 [n]) and, with_stats, a dict of the call's
+        rows_scanned / passes / kernel_ms: request i's page is rows[req_off[i]:req_off[i+1]], ascending
+        order key; next[i] is the next call's `after`, 0 on the last page."""
+        L = _lib.load()
+        reqs = np.ascontiguousarray(reqs, dtype=_lib.ROW_QUERY_DTYPE).reshape(-1)
+        n = reqs.shape[0]
+        buf = _lib.kg_query_buf()
+        _lib.check(L.kg_snapshot_query(self._h, _ptr(reqs) if n else None, n, C.byref(buf)), "kg_snapshot_query")
+        try:
+            m = int(buf.n_rows)
+            off = np.ctypeslib.as_array(buf.req_off, shape=(n + 1,)).copy()
+            if m:
+                rows = np.ctypeslib.as_array(C.cast(buf.rows, C.POINTER(C.c_uint32)), shape=(m, 6)).copy()
+                keys = np.ctypeslib.as_array(buf.keys, shape=(m,)).copy()
+            else:
+                rows, keys = np.zeros((0, 6), np.uint32), np.zeros(0, np.uint64)
+            nxt = np.ctypeslib.as_array(buf.next, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            matched = np.ctypeslib.as_array(buf.matched, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            stats = {"rows_scanned": int(buf.rows_scanned), "passes": int(buf.passes), "kernel_ms": float(buf.kernel_ms)}
+        finally:
+            L.kg_query_free(C.byref(buf))
+        return (rows, keys, off, nxt, matched, stats) if with_stats else (rows, keys, off, nxt, matched)
+
     def close(self) -> None:
         if self._h:
             _lib.load().kg_snapshot_destroy(self._h)
@@ -252,6 +278,17 @@ def queries_array(q6: np.ndarray, max_depths) -> np.ndarray:
     out = np.zeros((q6.shape[0], 7), np.uint32)
     out[:, :6] = q6
     out[:, 6] = np.broadcast_to(np.asarray(max_depths, np.int64), (q6.shape[0],)).astype(np.int32).view(np.uint32)
+    return out
+
+
+def row_queries(masks, tuples6, after=0, limit=100) -> np.ndarray:
+    """kg_row_query records from per-request masks (KG_Q_* bits), (n,6) tuple ids, `after` keys and limits."""
+    t = np.asarray(tuples6, np.uint32).reshape(-1, 6)
+    out = np.zeros(t.shape[0], _lib.ROW_QUERY_DTYPE)
+    out["mask"] = masks
+    out["t"] = t
+    out["after"] = after
+    out["limit"] = limit
     return out
 
 

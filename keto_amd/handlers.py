@@ -6,10 +6,12 @@ rule, status mirroring and the response shapes, as the reference's handlers do t
         GET/POST /relation-tuples/check/openapi    200 {"allowed": ...} always
                                                     internal/check/handler.go:101-232
         GET /relation-tuples/expand                 internal/expand/handler.go:81-107
+        GET /relation-tuples                        internal/relationtuple/read_server.go:122-175
         GET /relation-tuples/list-objects           no reference counterpart (ListObjectsHandler)
         GET /relation-tuples/list-subjects          no reference counterpart (ListSubjectsHandler)
   gRPC  CheckService.Check                          internal/check/handler.go:234-275
         ExpandService.Expand                        internal/expand/handler.go:109-146
+        ReadService.ListRelationTuples              internal/relationtuple/read_server.go:65-102
 
 An unknown namespace is "not allowed" over REST (handler.go:156-160, 221-225) but an error over gRPC
 (:261-264, the mapper's herodot.ErrNotFound).  Request errors are herodot's 400s
@@ -372,3 +374,88 @@ class ListSubjectsHandler:
                 raise _bad('incomplete request, provide "namespace", "object" and "relation"')
         return self._list(req["namespace"], req["object"], req["relation"], int(req.get("max_depth", 0)),
                           int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))
+
+
+def relation_query_from_url_query(q: dict):
+    """RelationQuery.FromURLQuery (ketoapi/enc_url_query.go:12-53): every field optional; a subject, where
+    one is given, as subject_from_url_query reads it."""
+    from .persister import RelationQuery
+    sid: Optional[str] = None
+    sset: Optional[SubjectSet] = None
+    if any(k in q for k in ("subject", SUBJECT_ID_KEY, SUBJECT_SET_NS_KEY, SUBJECT_SET_OBJ_KEY, SUBJECT_SET_REL_KEY)):
+        sid, sset = subject_from_url_query(q)
+    return RelationQuery(_get(q, "namespace") if "namespace" in q else None, _get(q, "object") if "object" in q else None,
+                         _get(q, "relation") if "relation" in q else None, sid, sset)
+
+
+def _subject_proto(t: RelationTuple) -> dict:
+    if t.subject_set is not None:
+        s = t.subject_set
+        return {"set": {"namespace": s.namespace, "object": s.object, "relation": s.relation}}
+    return {"id": t.subject_id}
+
+
+class RelationTuplesHandler:
+    """internal/relationtuple/read_server.go: REST GET /relation-tuples and gRPC ListRelationTuples over one
+    relationtuple.Manager (a SnapshotPersister, host or device reads)."""
+
+    def __init__(self, manager, mapper: Mapper):
+        self.manager, self.mapper = manager, mapper
+
+    def _list(self, query, page_token: str, page_size: int):
+        from .persister import MalformedPageToken
+        try:  # Mapper.FromQuery (uuid_mapping.go:60-120): the namespaces that are named must exist
+            if query.namespace is not None:
+                self.mapper.check_namespace(query.namespace)
+            if query.subject_set is not None:
+                self.mapper.check_namespace(query.subject_set.namespace)
+        except NamespaceNotFound as e:
+            raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        try:
+            return self.manager.get_relation_tuples(query, page_token, page_size)
+        except MalformedPageToken:
+            raise HandlerError(500, "malformed page token")  # a plain error: herodot's default status
+
+    def get_relations(self, query: Union[str, Query]) -> Tuple[int, dict]:
+        """GET /relation-tuples?namespace=&object=&relation=&subject_id= | subject_set.*=&page_token=&page_size=
+        (read_server.go:122-175)."""
+        try:
+            q = parse_query(query)
+            rq = relation_query_from_url_query(q)
+            size = 0
+            ps = _get(q, "page_size")
+            if ps != "":
+                try:
+                    size = parse_go_int(ps)
+                except ValueError:
+                    raise _bad(f"strconv.ParseInt: parsing {json.dumps(ps)}: invalid syntax")
+            tuples, token = self._list(rq, _get(q, "page_token"), size)
+        except HandlerError as e:
+            return e.status, e.body()
+        return 200, {"relation_tuples": [t.to_json() for t in tuples], "next_page_token": token}
+
+    def grpc_list_relation_tuples(self, req: dict) -> dict:
+        """ReadService.ListRelationTuples (read_server.go:65-102): req = {"relation_query": {...}} or the
+        deprecated {"query": {...}} whose empty strings mean unset, each with an optional "subject"
+        ({"id"} | {"set": {...}}), plus "page_size" and "page_token".  Raises HandlerError on failure."""
+        from .persister import RelationQuery
+        if req.get("relation_query") is not None:
+            src = req["relation_query"]
+            ns, obj, rel = src.get("namespace"), src.get("object"), src.get("relation")
+        elif req.get("query") is not None:
+            src = req["query"]
+            ns, obj, rel = (src.get(k) or None for k in ("namespace", "object", "relation"))
+        else:
+            raise _bad("you must provide a query")
+        sub = src.get("subject") or {}
+        sid, sset = None, None
+        if "id" in sub:
+            sid = sub["id"]
+        elif "set" in sub:
+            s = sub.get("set") or {}
+            sset = SubjectSet(s.get("namespace", ""), s.get("object", ""), s.get("relation", ""))
+        tuples, token = self._list(RelationQuery(ns, obj, rel, sid, sset), str(req.get("page_token", "")),
+                                   int(req.get("page_size", 0)))
+        return {"relation_tuples": [{"namespace": t.namespace, "object": t.object, "relation": t.relation,
+                                     "subject": _subject_proto(t)} for t in tuples],
+                "next_page_token": token}

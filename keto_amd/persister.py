@@ -23,7 +23,9 @@ INCREMENTALLY (``kg_snapshot_apply``: only the delta is interned on the host, ro
 derived structure are rebuilt on the device, inserted rows placed by shard id), so a check always
 sees every committed write (read-your-writes).  The first snapshot, and any delta larger than
 ``rebuild_fraction`` of the rows, is a full ``kg_snapshot_create_ordered``.  Reads of the tuple
-list (``get_relation_tuples``) are not on the hot path and are answered from the host rows.  Shard
+list (``get_relation_tuples``) are answered from the host rows, or -- ``device_reads=True`` -- from
+the refreshed snapshot (``kg_snapshot_query``: the filter and the page selection run on the device,
+the host maps one page of ids back to strings).  Shard
 ids come from a seeded generator so runs are reproducible (the reference draws them from
 crypto/rand; only their order matters, and no reference test pins it).
 """
@@ -38,9 +40,10 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 from sortedcontainers import SortedKeyList
 
-from .engine import Config, Engine, ExpandEngine, Snapshot
+from . import _lib
+from .engine import Config, Engine, ExpandEngine, Snapshot, row_queries
 from .ketoapi import RelationTuple, SubjectSet
-from .mapper import Interner, Mapper
+from .mapper import Interner, Mapper, SUBJECT_ID
 from .namespace import Namespace, compile_program
 
 DEFAULT_PAGE_SIZE = 100  # persister.go:38
@@ -88,7 +91,8 @@ class SnapshotPersister:
 
     def __init__(self, namespaces: Sequence[Namespace] = (), max_read_depth: int = 5, device: int = 0,
                  seed: int = 0, interner: Optional[Interner] = None, devices: Optional[Sequence[int]] = None,
-                 rebuild_fraction: float = 0.125):
+                 rebuild_fraction: float = 0.125, device_reads: bool = False):
+        self.device_reads = device_reads  # get_relation_tuples from the snapshot instead of the host rows
         self.interner = interner or Interner()
         self.namespaces = list(namespaces)
         self.config = Config(max_read_depth, self.namespaces)
@@ -165,6 +169,8 @@ class SnapshotPersister:
                 raise MalformedPageToken(page_token) from e
         else:
             last = 0  # uuid.Nil
+        if self.device_reads:
+            return self._device_page(query, last, per_page)
         res: List[Tuple[uuid.UUID, RelationTuple]] = []
         with self._lock:
             for sid, t in self._rows.irange_key(min_key=last, inclusive=(False, True)):  # shard_id > lastID
@@ -177,6 +183,40 @@ class SnapshotPersister:
             res = res[:per_page]
             token = str(res[-1][0])
         return [t for _, t in res], token
+
+    def _device_page(self, query: RelationQuery, last: int, per_page: int) -> Tuple[List[RelationTuple], str]:
+        """One page from the refreshed snapshot.  Strings map without interning: a string no tuple ever
+        had matches nothing.  The order key is the shard id's high half (_key), so is `after`; the token is
+        the full shard id of the page's last row, found in the host rows by its key."""
+        snap = self.snapshot()  # every committed write is in it
+        it = self.interner
+        mask, t = 0, [0] * 6
+        try:
+            if query.namespace is not None:
+                mask, t[0] = mask | _lib.KG_Q_NS, it.ns_id(query.namespace, create=False)
+            if query.object is not None:
+                mask, t[1] = mask | _lib.KG_Q_OBJ, it.obj_id(query.object, create=False)
+            if query.relation is not None:
+                mask, t[2] = mask | _lib.KG_Q_REL, it.rel_id(query.relation, create=False)
+            if query.subject_id is not None:
+                mask, t[3], t[4] = mask | _lib.KG_Q_SUBJECT, SUBJECT_ID, it.obj_id(query.subject_id, create=False)
+            elif query.subject_set is not None:
+                ss = query.subject_set
+                mask = mask | _lib.KG_Q_SUBJECT
+                t[3:6] = it.ns_id(ss.namespace, create=False), it.obj_id(ss.object, create=False), \
+                    it.rel_id(ss.relation, create=False)
+        except KeyError:
+            return [], ""
+        rows, keys, _, nxt, _ = snap.query(row_queries([mask], [t], self._key(last), per_page))
+        res = [it.relation_tuple(r) for r in rows]
+        token = ""
+        if int(nxt[0]):
+            k = int(nxt[0])
+            with self._lock:
+                hit = next(iter(self._rows.irange_key(min_key=k << 64, max_key=(k << 64) | ((1 << 64) - 1))), None)
+            # a row deleted since the snapshot: any id with its key continues behind it
+            token = str(hit[0] if hit is not None else uuid.UUID(int=(k << 64) | ((1 << 64) - 1)))
+        return res, token
 
     def __len__(self) -> int:
         return len(self._rows)
