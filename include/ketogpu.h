@@ -620,7 +620,16 @@ void kg_tree_free(kg_tree_buf* t);
  * err_code[i] is the code of the lowest such object id (0: none) -- an undeclared relation lists
  * nothing and reports every object of the namespace with KG_ERR_RELATION_NOT_FOUND.
  * Relations without a rewrite and materialised unions are answered by one reverse walk from the rows
- * that hold the subject (64 requests share a walk); every other relation by a check of every object.
+ * that hold the subject (64 requests share a walk).  A boolean rewrite -- and / or / not over at most 4
+ * such relations of the same object, e.g. share = view & !blocked -- whose formula is NotMember when
+ * every leaf is takes a bit of the same walk over its leaves: the objects the walk reaches through
+ * them, plus the objects with a row of rel itself or with a leaf node from which a rewrite or an error
+ * is reachable, are checked (each once), so the checks grow with what the subject reaches, not with the
+ * namespace.  For such a request exact counts nothing and candidates its checks.  Every other relation
+ * (a formula that is a member with every leaf NotMember, like not(view); tuple-to-subject-set or
+ * non-union leaves; undeclared relations; snapshots without reverse indexes) is answered by a check of
+ * every object.  kg_snapshot_tune key "lookup_formula" (default 1; tests, A/B runs): 0 = boolean
+ * rewrites are answered by a check of every object too; the answers do not depend on it.
  * Host buffer in; the output arrays are library-allocated pinned memory, returned by the free call below.
  * Request i owns objs[req_off[i] .. req_off[i+1]).  Thread-safe (a lane set per call, one replica,
  * rotated).  Hash-sharded snapshots: -3.  kg_snapshot_tune key "lookup_cap" (tests): initial entries
@@ -654,8 +663,11 @@ void kg_lookup_free(kg_lookup_buf* out);
  * err_code[i] is the code of the lowest one (0: none) -- an undeclared relation lists nothing and
  * reports every subject id with KG_ERR_RELATION_NOT_FOUND.
  * A pure root of a relation without a rewrite or of a materialised union is answered by one forward
- * walk over the set adjacency (64 requests share a walk; no reverse index is needed); every other
- * request by a check of every subject id.
+ * walk over the set adjacency (64 requests share a walk; no reverse index is needed).  A boolean
+ * rewrite as in kg_lookup_objects, on an object without a row of rel itself whose leaf nodes reach no
+ * rewrite and no error, walks from the object's leaf nodes (a walk bit each, at most 4) and checks the
+ * ids they list, each once: candidates counts those checks, exact nothing ("lookup_formula" 0: off).
+ * Every other request is answered by a check of every subject id.
  * The output is a kg_lookup_buf, returned by kg_lookup_free.  For this call: objs holds the ascending
  * subject ids per request (objs[req_off[i] .. req_off[i+1])); exact is the number of (request, id) keys
  * the walk emitted before duplicates are dropped (an id is usually reached through several nodes);

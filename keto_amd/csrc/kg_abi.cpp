@@ -567,6 +567,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     s->lookup_domain_rows = (int)value;
     return 0;
   }
+  if (strcmp(key, "lookup_formula") == 0) {
+    if (value < 0 || value > 1) return set_error(-2, "lookup_formula must be 0 or 1");
+    s->lookup_formula = (int)value;
+    return 0;
+  }
   if (strcmp(key, "query_cap") == 0) {
     if (value < 0 || value > (1ll << 32)) return set_error(-2, "query_cap must be in [0, 2^32]");
     s->query_cap = (uint64_t)value;

@@ -152,6 +152,8 @@ int Snapshot::build_formulas() {
   fp_leaves = 0;
   d_fidx = nullptr;
   d_fplans = nullptr;
+  h_fidx.clear();
+  h_fplans.clear();
   if (!materialize || !has_program) return 0;
   const uint32_t n_ns = ds.n_ns, n_rel = ds.n_rel;
   auto flag = [&](uint32_t ns, uint32_t r) -> uint8_t { return host_relflag(ns, r); };
@@ -245,11 +247,14 @@ int Snapshot::build_formulas() {
       P.own_rows = rs[(size_t)ns * n_rel + R] & 1u;
       for (uint32_t j = 0; j < P.n_leaves; j++)
         if (rs[(size_t)ns * n_rel + P.leaf[j]] & 2u) P.leaf_impure |= 1u << j;
+      fplan_lookup_facts(P);
     }
   if (alloc((void**)&d_fidx, idx.size() * 4) || alloc(&d_fplans, plans.size() * sizeof(FPlan))) return -1;
   HIPC(hipMemcpy(d_fidx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
   HIPC(hipMemcpy(d_fplans, plans.data(), plans.size() * sizeof(FPlan), hipMemcpyHostToDevice));
   n_fplans = (uint32_t)plans.size();
+  h_fidx = std::move(idx);  // the lookups plan their walks and candidate tables on the host
+  h_fplans = std::move(plans);
   return 0;
 }
 

@@ -5,17 +5,29 @@
 // The answer is defined through the check: for a request (ns, rel, subject, max_depth) the ascending
 // object ids o with a node (ns, o, *) for which CheckIsMember(ns:o#rel@subject, max_depth) is IsMember; for
 // (ns, obj, rel, max_depth) the subject ids of tuples with that check on ns:obj#rel.  An object request is
-// answered in one of three modes (k_lk_resolve):
+// answered in one of four modes (k_lk_resolve):
 //   reverse        (ns, rel) has no rewrite or is a materialised union, and the reverse indexes exist:
 //                  every member is a node of (ns, rel); a PURE node is a member iff its reverse distance
 //                  from a holder of the subject is <= D-1 (what k_back decides for one root), so one
 //                  target-free reverse walk lists them.  IMPURE nodes of (ns, rel) are confirmed.
 //   confirm-nodes  the same without reverse indexes: every node of (ns, rel) is confirmed.
-//   confirm-all    any other relation (interpreter / formula split / undeclared): every object of the
-//                  namespace is confirmed.
-// A subject request (k_ls_resolve) with a pure root of such a relation is answered by a FORWARD walk over
-// adj, everything else by confirming every subject id.  "Confirmed" = run through check_batch_device as
-// kg_query rows built on the device; no check kernel is touched.
+//   formula        (ns, rel) has a boolean-rewrite plan (kg_formula.hip) whose formula is NotMember when
+//                  every leaf is (FPlan::lookup_ok), and the reverse indexes exist: the request's bit of
+//                  the reverse walk listens to the plan's walk leaves J (FPlan::walk_leaves) instead of
+//                  (ns, rel), and a pure node of one that it reaches is a CANDIDATE, not an answer.  So
+//                  is the object of every impure node of (ns, rel) and of every leaf (J or not).  The
+//                  candidate keys are made unique and confirmed.  An object outside them has no node of
+//                  rel, its leaf nodes are absent or pure -- every leaf check is a definite answer
+//                  without an error -- and its J leaves are unreached, NotMember: f is NotMember.
+//   confirm-all    any other relation (interpreter / a plan with f(0) = true / undeclared; a formula
+//                  without reverse indexes or with kg_snapshot_tune "lookup_formula" 0): every object
+//                  of the namespace is confirmed.
+// A subject request (k_ls_resolve) with a pure root of a reverse-mode relation is answered by a FORWARD
+// walk over adj.  One on a lookup_ok plan whose object has no node of the relation and only pure leaf
+// nodes walks from its J-leaf roots: the ids they list are its candidates (an id none of them lists is
+// NotMember of every J leaf, so of f), made unique and confirmed.  Everything else confirms every
+// subject id.  "Confirmed" = run through check_batch_device as kg_query rows built on the device; no
+// check kernel is touched.
 //
 // There is one walk (walk_groups) with two direction policies (ReverseWalk, ForwardWalk).  It is level-
 // synchronous and bit-parallel over groups of 64 requests: a dense u64 visited mask per node (bit =
@@ -42,15 +54,15 @@ namespace {
 
 typedef unsigned long long u64;
 
-enum : uint32_t { LK_REVERSE = 0, LK_NODES = 1, LK_ALL = 2 };
+enum : uint32_t { LK_REVERSE = 0, LK_NODES = 1, LK_ALL = 2, LK_FORMULA = 3 };
 
 // A resolved request.
 struct LReq {
   uint32_t subj;    // tagged subject or NONE
   int32_t depth;    // clamped rest depth (>= 1)
   uint32_t mode;    // LK_*
-  uint32_t hfirst, hcount;  // the subject's holders hold[hfirst, hfirst + hcount) (reverse mode)
-  uint32_t pad;
+  uint32_t hfirst, hcount;  // the subject's holders hold[hfirst, hfirst + hcount) (reverse, formula mode)
+  uint32_t plan;            // formula mode: the relation's plan
 };
 
 // Device counters of one call.  Counts are TRUE counts: a count above its list's capacity means the
@@ -61,7 +73,8 @@ struct LkCtl {
   u64 ccount;     // candidate checks
   u64 dcount;     // domain keys (namespace slot << 32 | object)
   u64 confirmed;  // candidates answered IsMember
-  u64 nuniq;      // output keys after the duplicates are dropped
+  u64 nuniq;      // keys of a sorted list after the duplicates are dropped
+  u64 kcount;     // candidate keys of the formula requests (request << 32 | id)
   uint32_t fcount[2];  // the two frontier lists
   uint32_t tcount;     // touched nodes
   uint32_t over;       // a node list overflowed (they hold n_nodes entries: cannot happen)
@@ -70,7 +83,14 @@ struct LkCtl {
 // One request bit of a walk group.
 struct GReq {
   uint32_t ns, rel, req;
-  uint32_t root;  // forward walk: the request's root node
+  uint32_t root;  // forward walk: the bit's root node
+  // reverse walk: the relations of ns the bit listens to -- rel itself, or a formula request's walk leaves
+  uint32_t n_listen, listen[FP_LEAVES];
+};
+// A list of 64-bit keys a call fills step by step: `have` keys of the finished steps in a list of `cap`.
+// The list grows when a step's true count passes it; the step is then rerun.
+struct KeyList {
+  u64 cap = 0, have = 0;
 };
 
 struct Walk {
@@ -82,6 +102,9 @@ struct Walk {
   uint32_t lcap;      // entries of the node lists
   u64* okeys;         // output keys
   u64 ocap;
+  u64 fmask;          // the group's formula bits: what they list goes to the candidate keys
+  u64* kkeys;         // candidate keys
+  u64 kcap;
   const GReq* greq;   // the group's requests, by bit
   LkCtl* ctl;
 };
@@ -98,6 +121,13 @@ struct CandTab {
   const uint32_t* nsoff;  // [M + 1] into nsreq
   const uint32_t* nsreq;
   uint32_t M;
+  // the distinct (ns, rel) of the formula requests' relations and leaves, as keys / kall / koff / kreq: a
+  // node of one gives every request of the key a candidate KEY
+  const u64* fkeys;
+  const uint32_t* fall;
+  const uint32_t* foff;
+  const uint32_t* freq;
+  uint32_t FK;
 };
 
 // Appends val where pred; one atomic per wave; entries past cap are dropped and flagged.
@@ -141,8 +171,10 @@ __device__ __forceinline__ uint32_t lk_find(const T* a, uint32_t n, T key) {
 }
 
 // ------------------------------------------------------------------ request mapping
-__global__ __launch_bounds__(256) void k_lk_resolve(DevSnap s, const kg_lookup* __restrict__ q, uint32_t n,
-                                                    int32_t global, uint64_t hold_n, LReq* __restrict__ lr) {
+// fidx / plans: the formula plans (kg_formula.hip), nullptr: no request takes the formula mode.
+__global__ __launch_bounds__(256) void k_lk_resolve(DevSnap s, const int32_t* __restrict__ fidx,
+                                                    const FPlan* __restrict__ plans, const kg_lookup* __restrict__ q,
+                                                    uint32_t n, int32_t global, uint64_t hold_n, LReq* __restrict__ lr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const kg_lookup x = q[i];
@@ -153,30 +185,44 @@ __global__ __launch_bounds__(256) void k_lk_resolve(DevSnap s, const kg_lookup* 
     const uint32_t sn = nmap_find(s, x.sns, x.srel, x.sobj);
     subj = sn == NONE ? NONE : (SET_BIT | sn);
   }
-  const uint32_t mode =
+  uint32_t mode =
       (relflag(s, x.ns, x.rel) == 0 || rel_is_union(s, x.ns, x.rel)) ? (s.radj ? LK_REVERSE : LK_NODES) : LK_ALL;
+  uint32_t plan = 0;
+  if (mode == LK_ALL && fidx && s.radj && x.ns < s.n_ns && x.rel < s.n_rel) {
+    const int32_t p = fidx[(size_t)x.ns * s.n_rel + x.rel];
+    if (p >= 0 && plans[p].lookup_ok) {
+      mode = LK_FORMULA;
+      plan = (uint32_t)p;
+    }
+  }
   uint2 h = make_uint2(0, 0);
-  if (mode == LK_REVERSE) {
+  if (mode == LK_REVERSE || mode == LK_FORMULA) {
     h = holders_find(s, subj);
     if ((uint64_t)h.x + h.y > hold_n) h = make_uint2(0, 0);  // never read past hold[]
   }
-  lr[i] = LReq{subj, clamp_depth(x.max_depth, global), mode, h.x, h.y, 0};
+  lr[i] = LReq{subj, clamp_depth(x.max_depth, global), mode, h.x, h.y, plan};
 }
 
 // A resolved subject-lookup request.
-enum : uint32_t { LS_WALK = 0, LS_EMPTY = 1, LS_CONFIRM = 2 };
+enum : uint32_t { LS_WALK = 0, LS_EMPTY = 1, LS_CONFIRM = 2, LS_FORMULA = 3 };
 struct SReq {
   uint32_t root;  // root node (walk mode)
   int32_t depth;  // clamped rest depth (>= 1)
   uint32_t mode;  // LS_*
-  uint32_t pad;
+  uint32_t n_froot;           // formula mode: the object's nodes of the plan's walk leaves
+  uint32_t froot[FP_LEAVES];
 };
 
 // The subject-free part of k_resolve.  A relation without a rewrite or a materialised union: a missing
 // root answers every check NotMember (k_resolve routes it DONE), a pure root is walked, an impure one
-// confirmed.  Every other relation (interpreter, formula split, undeclared) is confirmed.
-__global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const kg_lookup_subj* __restrict__ q, uint32_t n,
-                                                    int32_t global, SReq* __restrict__ sr) {
+// confirmed.  A relation with a lookup_ok plan (fidx / plans; nullptr: none) whose object has no node of
+// the relation and no impure leaf node -- the condition under which k_fsplit splits its checks -- walks
+// from the object's nodes of the walk leaves, or is empty without one.  Every other relation
+// (interpreter, undeclared) is confirmed.
+__global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const int32_t* __restrict__ fidx,
+                                                    const FPlan* __restrict__ plans,
+                                                    const kg_lookup_subj* __restrict__ q, uint32_t n, int32_t global,
+                                                    SReq* __restrict__ sr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const kg_lookup_subj x = q[i];
@@ -186,7 +232,22 @@ __global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const kg_lookup_s
     if (root >= s.n_nodes) mode = LS_EMPTY;
     else mode = (s.nflags && (s.nflags[root] & NF_IMPURE)) ? LS_CONFIRM : LS_WALK;
   }
-  sr[i] = SReq{root, clamp_depth(x.max_depth, global), mode, 0};
+  SReq r{root, clamp_depth(x.max_depth, global), mode, 0, {NONE, NONE, NONE, NONE}};
+  if (mode == LS_CONFIRM && fidx && x.ns < s.n_ns && x.rel < s.n_rel) {
+    const int32_t p = fidx[(size_t)x.ns * s.n_rel + x.rel];
+    if (p >= 0 && plans[p].lookup_ok && nmap_find(s, x.ns, x.rel, x.obj) >= s.n_nodes) {
+      const FPlan& P = plans[p];
+      bool pure = true;
+      for (uint32_t j = 0; j < P.n_leaves && j < (uint32_t)FP_LEAVES; j++) {
+        const uint32_t v = nmap_find(s, x.ns, P.leaf[j], x.obj);
+        if (v >= s.n_nodes) continue;
+        if (s.nflags && (s.nflags[v] & NF_IMPURE)) pure = false;
+        else if ((P.walk_leaves >> j) & 1u) r.froot[r.n_froot++] = v;
+      }
+      if (pure) r.mode = r.n_froot ? LS_FORMULA : LS_EMPTY;
+    }
+  }
+  sr[i] = r;
 }
 
 // ------------------------------------------------------------------ the walk: arrivals and seeds
@@ -207,23 +268,32 @@ __device__ __forceinline__ u64 lk_mark(const DevSnap& s, const Walk& W, bool act
   return nb;
 }
 
-// Every request whose bit is in `bits` lists id (request << 32 | id).  Called by every lane of a wave.
+// Every request whose bit is in `bits` lists id (request << 32 | id): a formula bit into the candidate
+// keys, any other into the output keys.  Called by every lane of a wave.
 __device__ __forceinline__ void lk_list(const Walk& W, u64 bits, uint32_t id) {
-  u64 at = wave_reserve64(&W.ctl->ocount, (uint32_t)__popcll(bits));
-  for (; bits; bits &= bits - 1, at++)
-    if (at < W.ocap) W.okeys[at] = ((u64)W.greq[__ffsll(bits) - 1].req << 32) | id;
+  u64 ob = bits & ~W.fmask;
+  u64 at = wave_reserve64(&W.ctl->ocount, (uint32_t)__popcll(ob));
+  for (; ob; ob &= ob - 1, at++)
+    if (at < W.ocap) W.okeys[at] = ((u64)W.greq[__ffsll(ob) - 1].req << 32) | id;
+  if (!W.fmask) return;  // the same for every lane
+  u64 kb = bits & W.fmask;
+  at = wave_reserve64(&W.ctl->kcount, (uint32_t)__popcll(kb));
+  for (; kb; kb &= kb - 1, at++)
+    if (at < W.kcap) W.kkeys[at] = ((u64)W.greq[__ffsll(kb) - 1].req << 32) | id;
 }
 
-// The reverse walk's arrival: every new bit whose request asks for p's (ns, rel) lists p's object if p is
-// pure.  Impure nodes are candidates of the confirmation (every ancestor of one is impure too).
+// The reverse walk's arrival: every new bit that listens to p's (ns, rel) lists p's object if p is pure.
+// Impure nodes are candidates of the confirmation (every ancestor of one is impure too).
 __device__ __forceinline__ void lk_visit(const DevSnap& s, const Walk& W, bool act, uint32_t p, u64 m) {
   const u64 nb = lk_mark(s, W, act, p, m);
   u64 want = 0;
   if (nb && !(s.nflags && (s.nflags[p] & NF_IMPURE))) {
     const uint32_t pns = s.nd_ns[p], prel = s.nd_rel[p];
     for (u64 b = nb; b; b &= b - 1) {
-      const GReq g = W.greq[__ffsll(b) - 1];
-      if (g.ns == pns && g.rel == prel) want |= b & -b;  // the lowest bit of b
+      const GReq& g = W.greq[__ffsll(b) - 1];
+      bool hit = false;
+      for (uint32_t t = 0; t < g.n_listen && t < (uint32_t)FP_LEAVES; t++) hit |= g.listen[t] == prel;
+      if (g.ns == pns && hit) want |= b & -b;  // the lowest bit of b
     }
   }
   lk_list(W, want, want ? s.nd_obj[p] : 0u);
@@ -468,10 +538,12 @@ __device__ __forceinline__ void lk_emit_cands(uint32_t c, const uint32_t* reqs, 
 }
 
 // One pass over the nodes: the candidate nodes of the reverse / confirm-nodes requests become checks,
-// the objects of the confirm-all requests' namespaces become domain keys (sorted and deduplicated next);
-// on a refreshed snapshot only live nodes give one (DevSnap::nlive).
+// the objects of the confirm-all requests' namespaces become domain keys (sorted and deduplicated next)
+// and the nodes of the formula requests' relations and the impure nodes of their leaves candidate keys
+// (the same); on a refreshed snapshot only live nodes give a domain key (DevSnap::nlive).
 __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_lookup* __restrict__ q, kg_query* cq,
-                                                 uint32_t* creq, u64 ccap, u64* dkeys, u64 dcap, LkCtl* ctl) {
+                                                 uint32_t* creq, u64 ccap, u64* dkeys, u64 dcap, u64* kkeys, u64 kcap,
+                                                 LkCtl* ctl) {
   const uint32_t stride = gridDim.x * 256;
   for (uint32_t base = blockIdx.x * 256 + (threadIdx.x & ~63u); base < s.n_nodes; base += stride) {
     const uint32_t v = base + lane_id();
@@ -488,6 +560,38 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
     }
     lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
     lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
+    if (!T.FK) continue;  // the same for every lane
+    // formula requests: the node's object as a candidate key of every request of its (ns, rel)
+    uint32_t fc = 0, fk = 0;
+    if (v < s.n_nodes) {
+      // a node of the requests' own relation counts while it is live; a leaf's node when it is impure --
+      // then it has check rows, so its object occurs (nlive is about raw rows: a union node has none)
+      fk = lk_find(T.fkeys, T.FK, ((u64)s.nd_ns[v] << 32) | s.nd_rel[v]);
+      if (fk != NONE && (T.fall[fk] ? (!s.nlive || s.nlive[v]) : (s.nflags && (s.nflags[v] & NF_IMPURE))))
+        fc = T.foff[fk + 1] - T.foff[fk];
+    }
+    const u64 at = wave_reserve64(&ctl->kcount, fc);
+    for (uint32_t t = 0; t < fc; t++)
+      if (at + t < kcap) kkeys[at + t] = ((u64)T.freq[T.foff[fk] + t] << 32) | obj;
+  }
+}
+
+// The unique candidate keys (request << 32 | id) of the formula requests become the checks
+// cq[at, at + m): ns:id#rel@subject of an object lookup's request, ns:obj#rel@id of a subject lookup's.
+template <bool SUBJ, class Req>
+__global__ __launch_bounds__(256) void k_lk_key_cands(const u64* __restrict__ uk, u64 m, const Req* __restrict__ q,
+                                                      uint32_t n_reqs, kg_query* cq, uint32_t* creq) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
+    const u64 key = uk[i];
+    const uint32_t r = min((uint32_t)(key >> 32), n_reqs - 1), id = (uint32_t)key;
+    const Req x = q[r];
+    kg_query y;
+    if constexpr (SUBJ) y.t = kg_tuple{x.ns, x.obj, x.rel, KG_SUBJECT_ID, id, 0};
+    else y.t = kg_tuple{x.ns, id, x.rel, x.sns, x.sobj, x.srel};
+    y.max_depth = x.max_depth;
+    cq[i] = y;
+    creq[i] = r;
   }
 }
 
@@ -578,6 +682,7 @@ struct LookupBufs {
   DevBuf<uint32_t> creq, cerr;
   DevBuf<uint8_t> cout;
   DevBuf<u64> dkeys, dkeys2;
+  DevBuf<u64> kkeys, kkeys2;  // candidate keys of the formula requests
   DevBuf<u64> n_errors, errmin;
   // output
   DevBuf<u64> okeys, okeys2;
@@ -596,11 +701,9 @@ struct Call {
   Workspace* w;
   hipStream_t st;
   LookupBufs& B;
-  // The output keys (request << 32 | id): `have` of the finished steps in a list of `cap`.  The list
-  // grows when a step's true count passes it; the step is then rerun.
-  struct OutKeys {
-    u64 cap = 0, have = 0;
-  } O;
+  // The output keys (B.okeys) and the formula requests' candidate keys (B.kkeys; cap 0: the call has no
+  // formula request): request << 32 | id.
+  KeyList O, K;
   uint32_t grid_wide;
   int32_t gmax;
   size_t n = 0;
@@ -643,21 +746,47 @@ struct Call {
     return 0;
   }
 
-  // a list of at least `need` keys that keeps the finished steps', and the device counter back at them
-  int regrow_out(u64 need) {
-    O.cap = std::max<u64>(need, 2 * O.cap);
-    if (O.cap > B.okeys.cap()) {
+  // the candidate key list of a call with formula requests; starts at lookup_cap like the output keys
+  int want_cand_keys() {
+    K.cap = s->lookup_cap ? s->lookup_cap : std::max<u64>(65536, B.kkeys.cap());
+    HIPC(B.kkeys.reserve((size_t)K.cap));
+    return 0;
+  }
+
+  // a list of at least `need` keys that keeps the finished steps'
+  int regrow(KeyList& l, DevBuf<u64>& buf, u64 need) {
+    l.cap = std::max<u64>(need, 2 * l.cap);
+    if (l.cap > buf.cap()) {
       DevBuf<u64> nb;
-      HIPC(nb.reserve((size_t)O.cap));
-      if (O.have) HIPC(hipMemcpyAsync(nb.get(), B.okeys.get(), (size_t)O.have * 8, hipMemcpyDeviceToDevice, st));
+      HIPC(nb.reserve((size_t)l.cap));
+      if (l.have) HIPC(hipMemcpyAsync(nb.get(), buf.get(), (size_t)l.have * 8, hipMemcpyDeviceToDevice, st));
       HIPC(hipStreamSynchronize(st));
-      B.okeys = std::move(nb);
+      buf = std::move(nb);
     }
-    void* hb = w->host_buf(65536);
+    return 0;
+  }
+  // both device counters back at the finished steps' keys: the step that overflowed a list is rerun
+  int rewind() {
+    u64* hb = (u64*)w->host_buf(65536);
     if (!hb) return set_error(-1, "pinned host buffer");
-    memcpy(hb, &O.have, 8);
-    HIPC(hipMemcpyAsync(&B.ctl.get()->ocount, hb, 8, hipMemcpyHostToDevice, st));
-    HIPC(hipStreamSynchronize(st));  // the pinned word is reused by the next readback
+    hb[0] = O.have;
+    hb[1] = K.have;
+    HIPC(hipMemcpyAsync(&B.ctl.get()->ocount, &hb[0], 8, hipMemcpyHostToDevice, st));
+    HIPC(hipMemcpyAsync(&B.ctl.get()->kcount, &hb[1], 8, hipMemcpyHostToDevice, st));
+    HIPC(hipStreamSynchronize(st));  // the pinned words are reused by the next readback
+    return 0;
+  }
+  // after a step: true if a list was too small for the step's true counts h -- it has grown, the counters
+  // are rewound and the step runs again; false: the step's keys are kept
+  int settle(const LkCtl& h, bool* again) {
+    *again = h.ocount > O.cap || h.kcount > K.cap;
+    if (h.ocount > O.cap)
+      if (int rc = regrow(O, B.okeys, h.ocount)) return rc;
+    if (h.kcount > K.cap)
+      if (int rc = regrow(K, B.kkeys, h.kcount)) return rc;
+    if (*again) return rewind();
+    O.have = h.ocount;
+    K.have = h.kcount;
     return 0;
   }
 
@@ -695,14 +824,18 @@ int sort_keys(Call& c, DevBuf<K>& a, DevBuf<K>& b, size_t n, int end_bit, const 
   return 0;
 }
 
+// the bits of a key request << 32 | id of a call with n requests
+int key_bits(size_t n) {
+  int end_bit = 33;
+  while (end_bit < 64 && ((u64)n >> (end_bit - 32))) end_bit++;
+  return end_bit;
+}
+
 int Call::finish(kg_lookup_buf* out) {
   u64 m = 0;
   const u64* uk = B.okeys.get();
-  if (O.have) {
-    int end_bit = 33;
-    while (end_bit < 64 && ((u64)n >> (end_bit - 32))) end_bit++;
-    if (int rc = sort_keys(*this, B.okeys, B.okeys2, (size_t)O.have, end_bit, &uk, &m)) return rc;
-  }
+  if (O.have)
+    if (int rc = sort_keys(*this, B.okeys, B.okeys2, (size_t)O.have, key_bits(n), &uk, &m)) return rc;
   HIPC(B.d_off.reserve(n + 1));
   HIPC(B.d_objs.reserve((size_t)std::max<u64>(m, 1)));
   HIPC(B.d_ecode.reserve(n));
@@ -764,15 +897,32 @@ int collect(Call& c, u64 n_cand) {
     HIPC(hipGetLastError());
     LkCtl h;
     if (int rc = c.read_ctl(&h)) return rc;
-    if (h.ocount > c.O.cap) {
+    bool again = false;
+    if (int rc = c.settle(h, &again)) return rc;
+    if (again) {
       if (pass) return set_error(KG_ERR_RESOURCE_CODE, "lookup: output list overflowed twice");
-      if (int rc = c.regrow_out(h.ocount)) return rc;
       continue;
     }
-    c.O.have = h.ocount;
     c.n_conf = h.confirmed;
     return 0;
   }
+}
+
+// The call's candidate keys sorted, one of each: uk[0, *m).
+int unique_cand_keys(Call& c, const u64** uk, u64* m) {
+  return sort_keys(c, c.B.kkeys, c.B.kkeys2, (size_t)c.K.have, key_bits(c.n), uk, m);
+}
+
+// buf holds at least `need` entries and still its first `keep`.
+template <class T>
+int keep_grow(Call& c, DevBuf<T>& buf, size_t keep, size_t need) {
+  if (need <= buf.cap()) return 0;
+  DevBuf<T> nb;
+  HIPC(nb.reserve(std::max(need, 2 * buf.cap())));
+  if (keep) HIPC(hipMemcpyAsync(nb.get(), buf.get(), keep * sizeof(T), hipMemcpyDeviceToDevice, c.st));
+  HIPC(hipStreamSynchronize(c.st));
+  buf = std::move(nb);
+  return 0;
 }
 
 // ------------------------------------------------------------------ host: the walk
@@ -841,13 +991,15 @@ void launch_edges(Call& c, const Frontier& f, const Rows& r, const u64* pref, co
   hipLaunchKernelGGL(k_lk_frontier_edges<Body>, dim3(c.grid_wide), dim3(256), 0, c.st, f, r, pref, c.B.ctl.get(), body);
 }
 
-// The direction policies of walk_groups.  res: the resolved requests (.depth); seed(): the launch of
+// The direction policies of walk_groups.  res: the resolved requests (.depth); formula(): the request's
+// bits list candidate keys; seed(): the launch of
 // level 0 -- true: *F is its frontier's size, false: read it back; level(): the launches of level j >=
 // FIRST_LEVEL on the frontier f -- *expanded == false: they built no next frontier, the group's walk ends.
 //
 // Reverse: the seed lists the subject's holders; level j = 1 .. D-1 follows the frontier's reverse edges.
 struct ReverseWalk {
   const LReq* res;
+  bool formula(uint32_t req) const { return res[req].mode == LK_FORMULA; }
   static constexpr int32_t FIRST_LEVEL = 1;
   bool seed(Call& c, const Walk& W, const GReq*, uint32_t gn, uint32_t*) const {
     hipLaunchKernelGGL(k_lk_seed, dim3(gn), dim3(256), 0, c.st, c.s->ds, W, (const LReq*)c.B.d_res.get());
@@ -867,6 +1019,7 @@ struct ReverseWalk {
 // requests that go one level further (xlive), follows its adj rows (expand).
 struct ForwardWalk {
   const SReq* res;
+  bool formula(uint32_t req) const { return res[req].mode == LS_FORMULA; }
   Rows check;  // the check rows
   static constexpr int32_t FIRST_LEVEL = 0;
   // the first frontier is the group's distinct roots: no readback before level 0
@@ -907,8 +1060,11 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
     const uint32_t gn = (uint32_t)std::min<size_t>(64, greq.size() - g0);
     int32_t max_d = 1;
     for (uint32_t b = 0; b < gn; b++) max_d = std::max(max_d, dir.res[greq[g0 + b].req].depth);
+    u64 fmask = 0;
+    for (uint32_t b = 0; b < gn; b++)
+      if (dir.formula(greq[g0 + b].req)) fmask |= 1ull << b;
     Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), c.O.cap,
-           B.greq.get() + g0, B.ctl.get()};
+           fmask, B.kkeys.get(), c.K.cap, B.greq.get() + g0, B.ctl.get()};
     B.dirty = true;
     LkCtl h;
     uint32_t cur = 0, F = 0;
@@ -942,11 +1098,9 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
     if (!h_now)
       if (int rc = c.read_ctl(&h)) return rc;
     if (int rc = walk_finish(c, h)) return rc;
-    if (h.ocount > c.O.cap) {  // the group's keys did not fit: a larger list, the group again
-      if (int rc = c.regrow_out(h.ocount)) return rc;
-      continue;
-    }
-    c.O.have = h.ocount;
+    bool again = false;  // the group's keys did not fit: a larger list, the group again
+    if (int rc = c.settle(h, &again)) return rc;
+    if (again) continue;
     c.st_edges = h.edges;  // summed on the device over every run, reruns included
     g0 += gn;
   }
@@ -965,34 +1119,61 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
   hipStream_t st = c.st;
   const DevSnap& ds = s->ds;
   const LReq* lr = nullptr;
+  const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &lr, [&](uint32_t blocks, const kg_lookup* d_req, LReq* d_lr) {
-        hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, st, ds, d_req, (uint32_t)n, c.gmax,
-                           (uint64_t)s->n_check_rows, d_lr);
+        hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, st, ds, formula ? s->d_fidx : nullptr,
+                           (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, (uint64_t)s->n_check_rows, d_lr);
       }))
     return rc;
 
   // ---- plan: walk groups and candidate tables
   std::vector<GReq> greq;
-  std::map<u64, std::vector<uint32_t>> by_key;
+  std::map<u64, std::vector<uint32_t>> by_key, by_fkey;
   std::map<uint32_t, std::vector<uint32_t>> by_ns;
   for (size_t i = 0; i < n; i++) {
     if (lr[i].mode == LK_ALL) {
       by_ns[reqs[i].ns].push_back((uint32_t)i);
       continue;
     }
-    if (lr[i].mode == LK_REVERSE && lr[i].hcount) greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0});
+    if (lr[i].mode == LK_FORMULA) {
+      if (lr[i].plan >= s->h_fplans.size()) return set_error(-1, "lookup: formula plan out of range");
+      const FPlan& P = s->h_fplans[lr[i].plan];
+      // the walk listens to the walk leaves; the scan takes the relation and every leaf
+      GReq g{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 0, {}};
+      by_fkey[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
+      for (uint32_t j = 0; j < P.n_leaves && j < (uint32_t)FP_LEAVES; j++) {
+        by_fkey[((u64)reqs[i].ns << 32) | P.leaf[j]].push_back((uint32_t)i);
+        if ((P.walk_leaves >> j) & 1u) g.listen[g.n_listen++] = P.leaf[j];
+      }
+      if (lr[i].hcount && g.n_listen) greq.push_back(g);
+      continue;
+    }
+    if (lr[i].mode == LK_REVERSE && lr[i].hcount)
+      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 1, {reqs[i].rel}});
     // candidates of a reverse request: impure nodes -- none without node flags
     if (lr[i].mode == LK_NODES || ds.nflags) by_key[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
   }
+  if (!by_fkey.empty())
+    if (int rc = c.want_cand_keys()) return rc;
   if (int rc = walk_groups(c, greq, ReverseWalk{lr})) return rc;
 
   // ---- candidates: one pass over the nodes, then the sorted domains of the confirm-all namespaces
-  if (!by_key.empty() || !by_ns.empty()) {
+  if (!by_key.empty() || !by_ns.empty() || !by_fkey.empty()) {
     std::vector<uint32_t> blob;
-    const uint32_t K = (uint32_t)by_key.size(), M = (uint32_t)by_ns.size();
-    // layout (u32 words): keys[2K] | kall[K] | koff[K+1] | kreq[..] | nsv[M] | nsoff[M+1] | nsreq[..]
-    std::vector<u64> keys;
-    std::vector<uint32_t> kall, koff{0}, kreq, nsv, nsoff{0}, nsreq;
+    const uint32_t K = (uint32_t)by_key.size(), M = (uint32_t)by_ns.size(), FK = (uint32_t)by_fkey.size();
+    // layout (u32 words): keys[2K] | fkeys[2FK] | kall[K] | koff[K+1] | kreq[..] | nsv[M] | nsoff[M+1] | nsreq[..]
+    //                     | fall[FK] | foff[FK+1] | freq[..]
+    std::vector<u64> keys, fkeys;
+    std::vector<uint32_t> kall, koff{0}, kreq, nsv, nsoff{0}, nsreq, fall, foff{0}, freq;
+    for (auto& kv : by_fkey) {
+      fkeys.push_back(kv.first);
+      // every node of a request's own relation (its rows join the answer), the impure nodes of a leaf
+      bool own = false;
+      for (uint32_t r : kv.second) own |= reqs[r].rel == (uint32_t)kv.first;
+      fall.push_back(own ? 1u : 0u);
+      freq.insert(freq.end(), kv.second.begin(), kv.second.end());
+      foff.push_back((uint32_t)freq.size());
+    }
     for (auto& kv : by_key) {
       keys.push_back(kv.first);
       kall.push_back(lr[kv.second[0]].mode == LK_NODES ? 1u : 0u);
@@ -1004,20 +1185,22 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
       nsreq.insert(nsreq.end(), kv.second.begin(), kv.second.end());
       nsoff.push_back((uint32_t)nsreq.size());
     }
-    blob.resize(2 * (size_t)K);
+    blob.resize(2 * ((size_t)K + FK));
     if (K) memcpy(blob.data(), keys.data(), (size_t)K * 8);
+    if (FK) memcpy(blob.data() + 2 * (size_t)K, fkeys.data(), (size_t)FK * 8);
     auto put = [&blob](const std::vector<uint32_t>& v) {
       blob.insert(blob.end(), v.begin(), v.end());
       return blob.size() - v.size();
     };
     const size_t o_kall = put(kall), o_koff = put(koff), o_kreq = put(kreq), o_nsv = put(nsv), o_nsoff = put(nsoff),
-                 o_nsreq = put(nsreq);
+                 o_nsreq = put(nsreq), o_fall = put(fall), o_foff = put(foff), o_freq = put(freq);
     blob.push_back(0);
     HIPC(B.tab.reserve(blob.size() + 2));
     HIPC(hipMemcpyAsync(B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st));
     HIPC(hipStreamSynchronize(st));  // blob is pageable
     const uint32_t* tb = B.tab.get();
-    const CandTab T{(const u64*)tb, tb + o_kall, tb + o_koff, tb + o_kreq, K, tb + o_nsv, tb + o_nsoff, tb + o_nsreq, M};
+    const CandTab T{(const u64*)tb, tb + o_kall, tb + o_koff, tb + o_kreq, K, tb + o_nsv, tb + o_nsoff, tb + o_nsreq, M,
+                    (const u64*)tb + K, tb + o_fall, tb + o_foff, tb + o_freq, FK};
     const kg_lookup* d_req = (const kg_lookup*)B.d_req.get();
     u64 ccap = std::max<u64>(65536, B.cq.cap()), dcap = M ? std::max<u64>(65536, B.dkeys.cap()) : 0;
     for (;;) {
@@ -1025,14 +1208,19 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
       HIPC(B.creq.reserve((size_t)ccap));
       if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
       HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, st));  // ccount, dcount
+      if (FK)  // the candidate keys back at the walk's
+        if (int rc = c.rewind()) return rc;
       hipLaunchKernelGGL(k_lk_scan, dim3(std::max(1u, std::min(c.grid_wide, ds.n_nodes / 256 + 1))), dim3(256), 0, st, ds,
-                         T, d_req, B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap, B.ctl.get());
+                         T, d_req, B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap,
+                         B.ctl.get());
       HIPC(hipGetLastError());
       LkCtl h;
       if (int rc = c.read_ctl(&h)) return rc;
-      if (h.dcount > dcap) {
-        dcap = h.dcount;
+      if (h.dcount > dcap || h.kcount > c.K.cap) {
+        dcap = std::max(dcap, h.dcount);
         ccap = std::max(ccap, h.ccount);
+        if (h.kcount > c.K.cap)
+          if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
         continue;
       }
       if (h.ccount <= ccap && h.dcount) {
@@ -1049,8 +1237,22 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
         continue;
       }
       c.n_cand = h.ccount;
+      c.K.have = h.kcount;
       break;
     }
+  }
+  // ---- the formula requests' candidate keys, one of each, as checks behind the others
+  if (c.K.have) {
+    const u64* uk = nullptr;
+    u64 m = 0;
+    if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
+    if (int rc = keep_grow(c, B.cq, (size_t)c.n_cand, (size_t)(c.n_cand + m))) return rc;
+    if (int rc = keep_grow(c, B.creq, (size_t)c.n_cand, (size_t)(c.n_cand + m))) return rc;
+    hipLaunchKernelGGL((k_lk_key_cands<false, kg_lookup>), dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)),
+                       dim3(256), 0, st, uk, m, (const kg_lookup*)B.d_req.get(), (uint32_t)n, B.cq.get() + c.n_cand,
+                       B.creq.get() + c.n_cand);
+    HIPC(hipGetLastError());
+    c.n_cand += m;
   }
   if (c.n_cand) {
     HIPC(B.cout.reserve((size_t)c.n_cand));
@@ -1067,7 +1269,8 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
 }
 
 // kg_lookup_subjects on lane L (as lookup_objects).  Walk-mode requests are listed by the forward walk,
-// 64 per group; the others by a check of every subject id of the domain, in chunks of CHUNK pairs.
+// 64 bits per group; formula-mode requests take a bit per walk-leaf root there, and what those list is
+// checked; the others by a check of every subject id of the domain, in chunks of CHUNK pairs.
 int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
   Call c(s, L, gmax);
   LookupBufs& B = c.B;
@@ -1076,18 +1279,29 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
   const uint64_t n_rows = s->n_check_rows;
   const SReq* sr = nullptr;
+  const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj* d_req, SReq* d_sr) {
-        hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, st, ds, d_req, (uint32_t)n, c.gmax, d_sr);
+        hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, st, ds, formula ? s->d_fidx : nullptr,
+                           (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, d_sr);
       }))
     return rc;
 
-  std::vector<GReq> greq;      // walk mode, by group and bit
+  std::vector<GReq> greq;      // walk and formula mode, by group and bit
   std::vector<uint32_t> conf;  // confirm mode
+  bool any_formula = false;
   for (size_t i = 0; i < n; i++) {
     if (sr[i].mode == LS_WALK && sr[i].root < ds.n_nodes)
-      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root});
-    else if (sr[i].mode == LS_CONFIRM) conf.push_back((uint32_t)i);
+      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root, 0, {}});
+    else if (sr[i].mode == LS_FORMULA) {  // one bit per root of a walk leaf
+      for (uint32_t t = 0; t < sr[i].n_froot && t < (uint32_t)FP_LEAVES; t++)
+        if (sr[i].froot[t] < ds.n_nodes) {
+          greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].froot[t], 0, {}});
+          any_formula = true;
+        }
+    } else if (sr[i].mode == LS_CONFIRM) conf.push_back((uint32_t)i);
   }
+  if (any_formula)
+    if (int rc = c.want_cand_keys()) return rc;
   if (int rc = walk_groups(c, greq, ForwardWalk{sr, Rows{ds.crow_off ? ds.crow_off : ds.row_off, csub, n_rows}})) return rc;
 
   // ---- confirmation: the domain once, then every (subject id, request) pair through the check
@@ -1135,6 +1349,28 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
       const u64 m = std::min(CHUNK, c.n_cand - at);
       hipLaunchKernelGGL(k_ls_cands, dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)), dim3(256), 0, st, dom, n_dom,
                          (const uint32_t*)B.tab.get(), C, (const kg_lookup_subj*)B.d_req.get(), at, m, B.cq.get(),
+                         B.creq.get());
+      HIPC(hipGetLastError());
+      if (int rc = check_batch_device(s, c.w, B.cq.get(), (size_t)m, c.gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;
+      if (int rc = collect<true>(c, m)) return rc;
+    }
+  }
+  // ---- the formula requests' candidate keys, one of each, through the check in the same chunks
+  if (c.K.have) {
+    const u64* uk = nullptr;
+    u64 nk = 0;
+    if (int rc = unique_cand_keys(c, &uk, &nk)) return rc;
+    c.n_cand += nk;
+    constexpr u64 CHUNK = 1ull << 22;
+    const size_t ccap = (size_t)std::min(CHUNK, nk);
+    HIPC(B.cq.reserve(ccap));
+    HIPC(B.creq.reserve(ccap));
+    HIPC(B.cout.reserve(ccap));
+    HIPC(B.cerr.reserve(ccap));
+    for (u64 at = 0; at < nk; at += CHUNK) {
+      const u64 m = std::min(CHUNK, nk - at);
+      hipLaunchKernelGGL((k_lk_key_cands<true, kg_lookup_subj>), dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)),
+                         dim3(256), 0, st, uk + at, m, (const kg_lookup_subj*)B.d_req.get(), (uint32_t)n, B.cq.get(),
                          B.creq.get());
       HIPC(hipGetLastError());
       if (int rc = check_batch_device(s, c.w, B.cq.get(), (size_t)m, c.gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;

@@ -13,6 +13,7 @@
 
 #include "../../include/ketogpu.h"
 #include "kg_buf.h"
+#include "kg_formula.h"
 #include "kg_grid.h"
 #include "kg_internal.h"
 #include "kg_synth.h"
@@ -278,6 +279,8 @@ struct Snapshot {
   int32_t* d_fidx = nullptr;
   void* d_fplans = nullptr;
   uint32_t n_fplans = 0, fp_leaves = 0;  // plans, most leaves of one plan
+  std::vector<int32_t> h_fidx;           // host mirrors of both (kg_lookup.hip plans a call with them)
+  std::vector<FPlan> h_fplans;
   std::vector<std::pair<void*, size_t>> allocs;
   // host mirrors (host-tuple path); hmap + h_nd_* are handed on to a snapshot kg_snapshot_apply
   // builds from this one
@@ -357,6 +360,9 @@ struct Snapshot {
   // kg_snapshot_tune("lookup_domain_rows") (tests): 1 = kg_lookup_subjects lists its domain from the check
   // rows even where the holder bitmap exists (what a snapshot without reverse indexes does)
   int lookup_domain_rows = 0;
+  // kg_snapshot_tune("lookup_formula"): 1 = a lookup on a boolean rewrite takes its candidates from a walk
+  // over the plan's leaves; 0 = from the whole domain (tests, A/B: the answers are the same)
+  int lookup_formula = 1;
   uint64_t query_cap = 0;  // kg_snapshot_tune("query_cap"): (key, position) pairs a listing sorts directly (0 = 1 Mi; tests)
   uint64_t grid_ms_cap = 0;  // kg_snapshot_tune("grid_ms_cap"): MS-BFS entries per level buffer (0 = 16 Mi; tests)
   // replicas: the same snapshot on more devices (kg_snapshot_create's device mask); this object is

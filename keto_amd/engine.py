@@ -191,7 +191,8 @@ class Snapshot:
         """Engine knobs (kg_snapshot_tune; keto_amd/csrc/kg_abi.cpp tune_one lists them with their ranges;
         29 since round 6 removed the ones that measured flat, 30 with expand_hash_cap): tier chain -- back_wgs, back_edges, stream_ecap,
         stream_wgs, stream_steal, grid_wgs, grid_cap, grid_reserve, grid_ms, grid_ms_words, grid_ms_bytes,
-        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests); listing -- query_cap; expand -- expand_gw, expand_gw_wait_us,
+        grid_ms_tg_cap, grid_ms_cap, interp_cap2, max_lanes; lookup -- lookup_cap, lookup_domain_rows (tests), lookup_formula (0: boolean
+        rewrites take their candidates from the whole domain, not from a walk; same answers); listing -- query_cap; expand -- expand_gw, expand_gw_wait_us,
         expand_skip_lds (tests), expand_hash_cap (tests); hash-sharded -- shard_local, shard_force_exchange, shard_max_reruns,
         shard_max_bytes, shard_force_overflow (tests), shard_bucket, shard_vis, shard_heavy, shard_budget,
         shard_back_budget, shard_remote_meta (read at the first binding).  Build-time, from the environment:
@@ -406,7 +407,9 @@ class Engine:
                            with_stats: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """reqs: (n,6) uint32 kg_lookup rows (ns, rel, sns, sobj, srel, max_depth).  Returns (req_off u64
         [n+1], objs u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's objects are
-        objs[req_off[i]:req_off[i+1]] -- the objects of its namespace whose check is IsMember."""
+        objs[req_off[i]:req_off[i+1]] -- the objects of its namespace whose check is IsMember.  with_stats:
+        last_stats holds the call's counters; a request on a boolean rewrite (formula mode) counts its
+        checks in candidates and nothing in exact."""
         return self._lookup("kg_lookup_objects", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6), with_stats)
 
     def _lookup(self, call: str, reqs: np.ndarray, with_stats: bool):
@@ -450,7 +453,7 @@ class Engine:
         """reqs: (n,4) uint32 kg_lookup_subj rows (ns, obj, rel, max_depth).  Returns (req_off u64 [n+1],
         subject ids u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's subject ids
         are ids[req_off[i]:req_off[i+1]] -- the subject ids of the snapshot's tuples whose check on the
-        request's object is IsMember."""
+        request's object is IsMember.  last_stats as lookup_objects_ids."""
         return self._lookup("kg_lookup_subjects", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 4), with_stats)
 
     def lookup_subjects(self, namespace: str, object: str, relation: str, rest_depth: int) -> List[str]:

@@ -3,9 +3,17 @@ and for a batch of 64, and for the same requests every object of the namespace t
 kg_check_batch_device (queries resident in HBM, so the brute force pays no host transfer).
 
   python tools/lookup_bench.py [--mode objects|subjects] [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
+                               [--preset 0|1] [--relation NAME]
 
 --mode subjects measures the mirror image the same way: kg_lookup_subjects for one doc and for 64 docs
 against every subject id of the snapshot's tuples through kg_check_batch_device.
+
+--preset 1 builds the C3 graph with its program (keto_amd/synth.py) and asks for --relation, by default
+the permission doc#share = view & !blocked: a boolean rewrite, which the lookups answer in formula mode
+(candidates from a walk over the plan's leaves).  The lookup is then timed twice, with kg_snapshot_tune
+"lookup_formula" 1 and 0 (0: candidates from the whole domain; a library without the key is timed once, as
+it is), and each run's candidates / confirmed / n_objs are printed under "lookup_formula".  --relation
+view gives the number of doc#view members of the same subjects: what a share request's candidates must equal.
 
 Prints one JSON line: median wall-clock milliseconds of both paths, their ratio, and the lookup call's
 reverse_edges / levels / n_objs.  The two answers are compared before anything is timed.
@@ -32,14 +40,25 @@ def main(argv=None):
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--preset", type=int, choices=(0, 1), default=0)
+    ap.add_argument("--relation", default=None, help="default: viewer (preset 0), share (preset 1)")
     a = ap.parse_args(argv)
     import torch
     from keto_amd import _lib
     from keto_amd.engine import Config, Engine, Snapshot
     dev = torch.device("cuda", 0)
-    snap = Snapshot.synthetic(a.tuples)
+    snap = Snapshot.synthetic(a.tuples, preset=a.preset)
     eng = Engine(snap, Config(a.depth))
     L = _lib.load()
+    relation = a.relation or ("share" if a.preset else "viewer")
+    rel = snap.interner.rel_id(relation)
+    keys = [None]  # the values of "lookup_formula" the lookup is timed with
+    if a.preset:
+        try:
+            snap.tune("lookup_formula", 1)
+            keys = [1, 0]
+        except _lib.KetoGPUError:  # a library from before the key: its one mode
+            pass
     rows = snap.export()
     doc = rows[rows[:, 0] == NS_DOC]
     sets = rows[(rows[:, 3] == NS_DOC)]
@@ -50,8 +69,9 @@ def main(argv=None):
     mid = order[len(order) // 2 - 32:len(order) // 2 + 32]
     subj = users[mid]
     reqs64 = np.zeros((64, 6), np.uint32)
-    reqs64[:, 0], reqs64[:, 1], reqs64[:, 2], reqs64[:, 3] = NS_DOC, REL_VIEWER, SUBJECT_ID, subj
-    out = {"gpu": torch.cuda.get_device_name(0), "tuples": int(len(rows)), "nodes": snap.info()["nodes"],
+    reqs64[:, 0], reqs64[:, 1], reqs64[:, 2], reqs64[:, 3] = NS_DOC, rel, SUBJECT_ID, subj
+    out = {"gpu": torch.cuda.get_device_name(0), "preset": a.preset, "relation": relation, "tuples": int(len(rows)),
+           "nodes": snap.info()["nodes"],
            "domain_objects": int(len(domain)), "depth": a.depth, "holder_rows_of_user": int(deg[mid[32]])}
     if a.mode == "subjects":
         # mid-reach docs: the 64 doc#viewer nodes around the median check-row length; the domain is every subject id
@@ -61,14 +81,15 @@ def main(argv=None):
         mid = order[len(order) // 2 - 32:len(order) // 2 + 32]
         domain = users
         reqs64 = np.zeros((64, 4), np.uint32)
-        reqs64[:, 0], reqs64[:, 1], reqs64[:, 2] = NS_DOC, docs[mid], REL_VIEWER
-        out = {"gpu": out["gpu"], "tuples": out["tuples"], "nodes": out["nodes"], "domain_subject_ids": int(len(domain)),
+        reqs64[:, 0], reqs64[:, 1], reqs64[:, 2] = NS_DOC, docs[mid], rel
+        out = {"gpu": out["gpu"], "preset": a.preset, "relation": relation, "tuples": out["tuples"], "nodes": out["nodes"],
+               "domain_subject_ids": int(len(domain)),
                "depth": a.depth, "check_row_of_doc": int(rlen[mid[32]])}
     stream = torch.cuda.current_stream(dev)
     for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
         n = len(reqs)
         q = torch.zeros((n, len(domain), 7), dtype=torch.int32, device=dev)  # kg_query rows, built in HBM
-        q[:, :, 0], q[:, :, 2], q[:, :, 3] = NS_DOC, REL_VIEWER, -1  # -1: KG_SUBJECT_ID
+        q[:, :, 0], q[:, :, 2], q[:, :, 3] = NS_DOC, rel, -1  # -1: KG_SUBJECT_ID
         d_dom = torch.from_numpy(domain.view(np.int32)).to(dev)[None, :]
         d_req = torch.from_numpy(reqs[:, 3 if a.mode == "objects" else 1].copy().view(np.int32)).to(dev)[:, None]
         q[:, :, 1], q[:, :, 4] = (d_dom, d_req) if a.mode == "objects" else (d_req, d_dom)
@@ -86,27 +107,39 @@ def main(argv=None):
                 return eng.lookup_subjects_ids(reqs, with_stats=True)
             return eng.lookup_objects_ids(reqs, with_stats=True)
 
-        brute()
-        off, objs, err, nerr = lookup()
-        member = (d_out.cpu().numpy() == 1).reshape(n, len(domain))
-        for i in range(n):  # the same answer both ways, before anything is timed
-            assert np.array_equal(objs[int(off[i]):int(off[i + 1])], domain[member[i]]), i
-        assert not nerr.any()
-        t = {}
-        for what, fn in (("lookup_ms", lookup), ("brute_ms", brute)):
+        def median_ms(fn):
             xs = []
             for k in range(a.warmup + a.reps):
                 t0 = time.perf_counter()
                 fn()
                 if k >= a.warmup:
                     xs.append((time.perf_counter() - t0) * 1e3)
-            t[what] = statistics.median(xs)
-        lookup()
-        st = eng.last_stats
+            return statistics.median(xs)
+
+        brute()
+        member = (d_out.cpu().numpy() == 1).reshape(n, len(domain))
+        t, by_key = {}, {}
+        for key in reversed(keys):  # the default (None, or 1) last: its figures are the entry's own
+            if key is not None:
+                snap.tune("lookup_formula", key)
+            off, objs, err, nerr = lookup()
+            for i in range(n):  # the same answer both ways, before anything is timed
+                assert np.array_equal(objs[int(off[i]):int(off[i + 1])], domain[member[i]]), (key, i)
+            assert not nerr.any()
+            t["lookup_ms"] = median_ms(lookup)
+            lookup()
+            st = eng.last_stats
+            by_key[str(key)] = {"lookup_ms": round(t["lookup_ms"], 4), "lookup_kernel_ms": round(st["kernel_ms"], 4),
+                                "candidates": int(st["candidates"]), "confirmed": int(st["confirmed"]),
+                                "n_objs": int(st["n_objs"])}
+        t["brute_ms"] = median_ms(brute)
         out[name] = {"requests": n, "checks_brute": int(dq.shape[0]), "lookup_ms": round(t["lookup_ms"], 4),
                      "brute_ms": round(t["brute_ms"], 4), "brute_over_lookup": round(t["brute_ms"] / t["lookup_ms"], 2),
                      "lookup_kernel_ms": round(st["kernel_ms"], 4), "reverse_edges": int(st["reverse_edges"]),
-                     "levels": int(st["levels"]), "n_objs": int(st["n_objs"]), "exact": int(st["exact"]), "candidates": int(st["candidates"])}
+                     "levels": int(st["levels"]), "n_objs": int(st["n_objs"]), "exact": int(st["exact"]), "candidates": int(st["candidates"]),
+                     "confirmed": int(st["confirmed"])}
+        if a.preset:
+            out[name]["lookup_formula"] = by_key
         del q, dq, d_out, d_err
     print(json.dumps(out))
 
