@@ -683,6 +683,45 @@ typedef struct {
 int kg_lookup_subjects(kg_snapshot* s, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
                        kg_lookup_buf* out);
 
+/* ---- paged lookups ----------------------------------------------------------------------- */
+/* The next `limit` ids of a lookup's answer from a cursor (OpenFGA ListObjects caps its result; SpiceDB
+ * LookupResources / LookupSubjects take a cursor and a limit).  The page is defined through the unpaged
+ * call: for request i let A be the ascending answer of kg_lookup_objects / kg_lookup_subjects and E the
+ * ascending ids that call counts in n_errors.  The paged call returns the first `limit` ids of
+ * {a in A : a >= from}; next[i] is KG_LOOKUP_END when A holds no further id at or above `from`, else the
+ * page's last id + 1.  The page covers the ids [from, next) (END: to the top of the id space):
+ * list.n_errors[i] is the number of ids of E in that range and list.err_code[i] the code of the lowest one
+ * (0: none).  Reading pages from from = 0 until END gives A exactly once; the n_errors of the pages sum to
+ * the unpaged count and the first non-zero err_code is the unpaged one.  An undeclared relation lists
+ * nothing and covers [from, END): it reports every id at or above `from`.  from = 0 with limit =
+ * 0xFFFFFFFF returns the unpaged call's arrays.  limit == 0: -2.  A `from` above every id: an empty page
+ * and END.  Hash-sharded snapshots: -3.  Threading, lanes, the replica rotation and "lookup_cap" as the
+ * unpaged calls.
+ * How: the walk never emits a key below its request's `from`; every candidate of a confirmation becomes
+ * a key (request, id) >= from, sorted and made unique, and is checked in ascending rounds: a request's
+ * first round takes at most 64 candidates, each later round at most doubles what it has checked, and the
+ * request stops once limit + 1 members lie at or below the largest id it has checked (or its candidates
+ * run out).  Only the pages' ids cross the bus.  The walk still visits everything the subject or object
+ * reaches and its key list can grow to that size.
+ * list: layout and meaning of the unpaged call with objs holding only the pages' ids; exact counts the
+ * keys the walk emitted (ids >= from only), candidates the checks run, confirmed the members among them.
+ * Returned by kg_lookup_pages_free. */
+#define KG_LOOKUP_END 0xFFFFFFFFu
+typedef struct {
+  uint32_t from, limit; /* ids >= from, at most limit of them (limit >= 1) */
+} kg_lookup_page;
+typedef struct {
+  kg_lookup_buf list;
+  uint32_t* next;  /* per request: the next call's `from`, or KG_LOOKUP_END */
+  uint64_t rounds; /* confirmation rounds the call ran */
+  uint64_t pinned; /* library use */
+} kg_lookup_pages;
+int kg_lookup_objects_page(kg_snapshot* s, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n,
+                           int32_t global_max_depth, kg_lookup_pages* out);
+int kg_lookup_subjects_page(kg_snapshot* s, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+                            int32_t global_max_depth, kg_lookup_pages* out);
+void kg_lookup_pages_free(kg_lookup_pages* out);
+
 /* ---- tuple listing ----------------------------------------------------------------------- */
 /* GetRelationTuples (GET /relation-tuples, ReadService.ListRelationTuples; relationtuple.Manager over a
  * RelationQuery, internal/persistence/sql/relationtuples.go:124-145,203-244) on the device snapshot:

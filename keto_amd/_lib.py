@@ -107,6 +107,18 @@ class kg_lookup_buf(C.Structure):
                 ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
 
 
+KG_LOOKUP_END = 0xFFFFFFFF
+
+
+class kg_lookup_page(C.Structure):
+    _fields_ = [("from_", C.c_uint32), ("limit", C.c_uint32)]
+
+
+class kg_lookup_pages(C.Structure):
+    _fields_ = [("list", kg_lookup_buf), ("next", C.POINTER(C.c_uint32)), ("rounds", C.c_uint64),
+                ("pinned", C.c_uint64)]
+
+
 KG_Q_NS, KG_Q_OBJ, KG_Q_REL, KG_Q_SUBJECT = 1, 2, 4, 8
 
 
@@ -144,7 +156,8 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_held_words", "kg_shard_held", "kg_shard_result_slots", "kg_shard_bad_nodes", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats", "kg_batcher_reset_stats", "kg_batcher_destroy",
            "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
            "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
-           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free"]
+           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free",
+           "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -224,6 +237,14 @@ def load(path: str = LIB_PATH):
     L.kg_lookup_subjects.restype = C.c_int
     L.kg_lookup_free.argtypes = [C.POINTER(kg_lookup_buf)]
     L.kg_lookup_free.restype = None
+    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_objects_page"):
+        # (an A/B build from before the paged calls, loaded through KG_LIB_PATH, goes without them)
+        L.kg_lookup_objects_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
+        L.kg_lookup_objects_page.restype = C.c_int
+        L.kg_lookup_subjects_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
+        L.kg_lookup_subjects_page.restype = C.c_int
+        L.kg_lookup_pages_free.argtypes = [C.POINTER(kg_lookup_pages)]
+        L.kg_lookup_pages_free.restype = None
     L.kg_snapshot_query.argtypes = [vp, vp, sz, C.POINTER(kg_query_buf)]
     L.kg_snapshot_query.restype = C.c_int
     L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]

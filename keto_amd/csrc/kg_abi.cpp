@@ -1056,6 +1056,42 @@ void kg_lookup_free(kg_lookup_buf* out) {
   if (out) kg::lookup_free(out);
 }
 
+// The paged calls: the page arguments are checked before anything else, then one lane as above.
+extern "C++" template <class Req, class Run>
+static int lookup_page_call(const char* name, kg_snapshot* sp, const Req* reqs, const kg_lookup_page* pages, size_t n,
+                            kg_lookup_pages* out, Run run) {
+  if (!out) return set_error(-2, "NULL argument");
+  memset(out, 0, sizeof *out);
+  if (n && !pages) return set_error(-2, "pages is NULL");
+  for (size_t i = 0; i < n; i++)
+    if (pages[i].limit == 0) return set_error(-2, "%s: page %zu has limit 0", name, i);
+  return lookup_call(name, sp, reqs, n, &out->list, false, [&](Snapshot* rep, kg::Lane* L) { return run(rep, L); });
+}
+
+int kg_lookup_objects_page(kg_snapshot* sp, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n,
+                           int32_t global_max_depth, kg_lookup_pages* out) {
+  KG_GUARD_BEGIN
+  return lookup_page_call("kg_lookup_objects_page", sp, reqs, pages, n, out, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_objects_page(rep, L, reqs, pages, n, global_max_depth, out);
+  });
+  KG_GUARD_END
+}
+
+int kg_lookup_subjects_page(kg_snapshot* sp, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+                            int32_t global_max_depth, kg_lookup_pages* out) {
+  KG_GUARD_BEGIN
+  return lookup_page_call("kg_lookup_subjects_page", sp, reqs, pages, n, out, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_subjects_page(rep, L, reqs, pages, n, global_max_depth, out);
+  });
+  KG_GUARD_END
+}
+
+void kg_lookup_pages_free(kg_lookup_pages* out) {
+  if (!out) return;
+  kg::lookup_free(&out->list);  // next lies in the list's block
+  memset(out, 0, sizeof *out);
+}
+
 // A hash-sharded snapshot lists its own rank's rows, as kg_snapshot_rows.
 int kg_snapshot_query(kg_snapshot* sp, const kg_row_query* reqs, size_t n, kg_query_buf* out) {
   KG_GUARD_BEGIN

@@ -34,6 +34,16 @@
 // request), a frontier list per level, work assigned per edge through a prefix over the frontier rows'
 // lengths.  The masks are cleared by replaying the list of touched nodes, so a lookup costs what it
 // reaches, not n_nodes.
+//
+// The paged calls (kg_lookup_objects_page / kg_lookup_subjects_page: the first `limit` ids >= `from` of the
+// unpaged answer) run the same steps with three differences.  A walk bit lists no id below its request's
+// cursor (GReq::from).  Every candidate of a confirmation becomes a key request << 32 | id at or above the
+// cursor -- the subject lookup's confirm requests index the ascending domain instead -- and no check is
+// built up front: the sorted unique keys are checked in ascending rounds (page_rounds), at most 64 of a
+// request first, then at most as many again as it has checked, until limit + 1 of its members (walk keys
+// and confirmed candidates) lie at or below the largest id it has checked, or its candidates run out.
+// A walk key above that id stays unplaced: an unchecked candidate may lie below it.  Last, one kernel cuts
+// every request's page out of the sorted unique keys and only the pages go into the pinned block.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -78,6 +88,8 @@ struct LkCtl {
   uint32_t fcount[2];  // the two frontier lists
   uint32_t tcount;     // touched nodes
   uint32_t over;       // a node list overflowed (they hold n_nodes entries: cannot happen)
+  u64 ptotal;          // paged calls: the candidates of the round being built / the ids of the pages
+  u64 ecount;          // paged calls: erring (request, id) keys collected
 };
 
 // One request bit of a walk group.
@@ -86,7 +98,18 @@ struct GReq {
   uint32_t root;  // forward walk: the bit's root node
   // reverse walk: the relations of ns the bit listens to -- rel itself, or a formula request's walk leaves
   uint32_t n_listen, listen[FP_LEAVES];
+  uint32_t from;  // paged calls: the request's cursor -- the bit lists no id below it
 };
+// A request of a paged call: its page, and its run of candidates -- [lo, hi) of the call's sorted unique
+// candidate keys or, `implicit` (a subject lookup's confirm request), of the ascending subject domain.
+// The rounds check [lo, cur); the round being built takes [base, cur).
+struct PgReq {
+  u64 lo, hi, cur, base;
+  u64 nmem;  // members among the checked candidates
+  uint32_t from, limit;
+  uint32_t implicit, pad;
+};
+
 // A list of 64-bit keys a call fills step by step: `have` keys of the finished steps in a list of `cap`.
 // The list grows when a step's true count passes it; the step is then rerun.
 struct KeyList {
@@ -107,6 +130,7 @@ struct Walk {
   u64 kcap;
   const GReq* greq;   // the group's requests, by bit
   LkCtl* ctl;
+  bool paged;         // a paged call: a bit lists only the ids at or above its request's cursor
 };
 
 // The candidate tables of a call: the distinct (ns, rel) of its reverse / confirm-nodes requests and
@@ -271,6 +295,12 @@ __device__ __forceinline__ u64 lk_mark(const DevSnap& s, const Walk& W, bool act
 // Every request whose bit is in `bits` lists id (request << 32 | id): a formula bit into the candidate
 // keys, any other into the output keys.  Called by every lane of a wave.
 __device__ __forceinline__ void lk_list(const Walk& W, u64 bits, uint32_t id) {
+  if (W.paged) {  // the same for every lane
+    u64 keep = 0;
+    for (u64 b = bits; b; b &= b - 1)
+      if (id >= W.greq[__ffsll(b) - 1].from) keep |= b & -b;
+    bits = keep;
+  }
   u64 ob = bits & ~W.fmask;
   u64 at = wave_reserve64(&W.ctl->ocount, (uint32_t)__popcll(ob));
   for (; ob; ob &= ob - 1, at++)
@@ -537,13 +567,30 @@ __device__ __forceinline__ void lk_emit_cands(uint32_t c, const uint32_t* reqs, 
   }
 }
 
+// A paged call's candidates of object obj: a candidate key (request << 32 | obj) for every request of
+// reqs[0, c) whose cursor obj has reached.  Called by every lane of a wave.
+__device__ __forceinline__ void lk_emit_keys(uint32_t c, const uint32_t* reqs, uint32_t obj,
+                                             const PgReq* __restrict__ pg, u64* kkeys, u64 kcap, LkCtl* ctl) {
+  uint32_t k = 0;
+  for (uint32_t t = 0; t < c; t++) k += obj >= pg[reqs[t]].from ? 1u : 0u;
+  u64 at = wave_reserve64(&ctl->kcount, k);
+  for (uint32_t t = 0; t < c; t++) {
+    const uint32_t r = reqs[t];
+    if (obj < pg[r].from) continue;
+    if (at < kcap) kkeys[at] = ((u64)r << 32) | obj;
+    at++;
+  }
+}
+
 // One pass over the nodes: the candidate nodes of the reverse / confirm-nodes requests become checks,
 // the objects of the confirm-all requests' namespaces become domain keys (sorted and deduplicated next)
 // and the nodes of the formula requests' relations and the impure nodes of their leaves candidate keys
-// (the same); on a refreshed snapshot only live nodes give a domain key (DevSnap::nlive).
+// (the same); on a refreshed snapshot only live nodes give a domain key (DevSnap::nlive).  PAGED (pg: the
+// requests' pages): no check is built -- every candidate at or above its request's cursor is a key.
+template <bool PAGED>
 __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_lookup* __restrict__ q, kg_query* cq,
                                                  uint32_t* creq, u64 ccap, u64* dkeys, u64 dcap, u64* kkeys, u64 kcap,
-                                                 LkCtl* ctl) {
+                                                 const PgReq* __restrict__ pg, LkCtl* ctl) {
   const uint32_t stride = gridDim.x * 256;
   for (uint32_t base = blockIdx.x * 256 + (threadIdx.x & ~63u); base < s.n_nodes; base += stride) {
     const uint32_t v = base + lane_id();
@@ -558,7 +605,8 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
       // the domain: objects that occur in a tuple -- not the node a refresh left behind without one
       if (T.M && (!s.nlive || s.nlive[v])) slot = lk_find(T.nsv, T.M, ns);
     }
-    lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
+    if constexpr (PAGED) lk_emit_keys(c, c ? T.kreq + T.koff[k] : nullptr, obj, pg, kkeys, kcap, ctl);
+    else lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
     lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
     if (!T.FK) continue;  // the same for every lane
     // formula requests: the node's object as a candidate key of every request of its (ns, rel)
@@ -570,9 +618,13 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
       if (fk != NONE && (T.fall[fk] ? (!s.nlive || s.nlive[v]) : (s.nflags && (s.nflags[v] & NF_IMPURE))))
         fc = T.foff[fk + 1] - T.foff[fk];
     }
-    const u64 at = wave_reserve64(&ctl->kcount, fc);
-    for (uint32_t t = 0; t < fc; t++)
-      if (at + t < kcap) kkeys[at + t] = ((u64)T.freq[T.foff[fk] + t] << 32) | obj;
+    if constexpr (PAGED) {
+      lk_emit_keys(fc, fc ? T.freq + T.foff[fk] : nullptr, obj, pg, kkeys, kcap, ctl);
+    } else {
+      const u64 at = wave_reserve64(&ctl->kcount, fc);
+      for (uint32_t t = 0; t < fc; t++)
+        if (at + t < kcap) kkeys[at + t] = ((u64)T.freq[T.foff[fk] + t] << 32) | obj;
+    }
   }
 }
 
@@ -596,10 +648,12 @@ __global__ __launch_bounds__(256) void k_lk_key_cands(const u64* __restrict__ uk
 }
 
 // The sorted domain keys: the first key of every run is one object of the namespace; it becomes a check
-// for every confirm-all request of that namespace.
+// for every confirm-all request of that namespace -- PAGED: a candidate key, as k_lk_scan.
+template <bool PAGED>
 __global__ __launch_bounds__(256) void k_lk_domain(CandTab T, const u64* __restrict__ dk, u64 nd,
                                                    const kg_lookup* __restrict__ q, kg_query* cq, uint32_t* creq,
-                                                   u64 ccap, LkCtl* ctl) {
+                                                   u64 ccap, u64* kkeys, u64 kcap, const PgReq* __restrict__ pg,
+                                                   LkCtl* ctl) {
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < nd; base += stride) {
     const u64 i = base + lane_id();
@@ -612,7 +666,8 @@ __global__ __launch_bounds__(256) void k_lk_domain(CandTab T, const u64* __restr
         if (slot < T.M) c = T.nsoff[slot + 1] - T.nsoff[slot];
       }
     }
-    lk_emit_cands(c, c ? T.nsreq + T.nsoff[slot] : nullptr, obj, q, cq, creq, ccap, ctl);
+    if constexpr (PAGED) lk_emit_keys(c, c ? T.nsreq + T.nsoff[slot] : nullptr, obj, pg, kkeys, kcap, ctl);
+    else lk_emit_cands(c, c ? T.nsreq + T.nsoff[slot] : nullptr, obj, q, cq, creq, ccap, ctl);
   }
 }
 
@@ -661,6 +716,220 @@ __global__ __launch_bounds__(256) void k_lk_finish(const u64* __restrict__ uk, u
   }
 }
 
+// ------------------------------------------------------------------ paged calls: rounds and the page
+constexpr u64 PG_FIRST = 64;            // a request's first round checks at most this many candidates
+constexpr u64 PG_ROUND_MAX = 1ull << 22;  // and no round more than this many of one request
+
+// the id of entry i of request x's run of candidates
+__device__ __forceinline__ uint32_t pg_cand(const PgReq& x, u64 i, const u64* __restrict__ uk,
+                                            const uint32_t* __restrict__ dom) {
+  return x.implicit ? dom[i] : (uint32_t)uk[i];
+}
+
+// The requests' runs: of the sorted unique candidate keys uk[0, m), or of the domain dom[0, n_dom) from
+// the cursor on.
+__global__ __launch_bounds__(256) void k_pg_init(PgReq* pg, uint32_t n, const u64* __restrict__ uk, u64 m,
+                                                 const uint32_t* __restrict__ dom, u64 n_dom) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  PgReq x = pg[i];
+  if (x.implicit) {
+    x.lo = lk_lower_bound(dom, n_dom, x.from);
+    x.hi = n_dom;
+  } else {
+    x.lo = lk_lower_bound(uk, m, ((u64)i << 32) | x.from);
+    x.hi = lk_lower_bound(uk, m, ((u64)i + 1) << 32);
+  }
+  x.cur = x.base = x.lo;
+  x.nmem = 0;
+  pg[i] = x;
+}
+
+// What request i takes in the next round.  X: the largest candidate id it has checked; it is finished
+// when limit + 1 members -- the walk's keys xk[0, mx) (sorted, unique) and the confirmed candidates -- lie
+// at or below X: a key above X cannot be placed while an unchecked candidate may lie below it.
+struct PgTake {
+  PgReq* pg;
+  const u64* uk;
+  const uint32_t* dom;
+  const u64* xk;
+  u64 mx;
+  __device__ u64 operator()(uint32_t i) const {
+    PgReq& x = pg[i];
+    const u64 cur = x.cur, left = x.hi - cur, done = cur - x.lo;
+    u64 take = 0;
+    if (left) {
+      bool full = false;
+      if (done) {
+        const u64 top = (((u64)i << 32) | pg_cand(x, cur - 1, uk, dom)) + 1;
+        const u64 below = lk_lower_bound(xk, mx, top) - lk_lower_bound(xk, mx, ((u64)i << 32) | x.from);
+        full = x.nmem + below >= (u64)x.limit + 1;
+      }
+      if (!full) take = min(left, done ? min(done, PG_ROUND_MAX) : PG_FIRST);
+    }
+    x.base = cur;
+    x.cur = cur + take;
+    return take;
+  }
+};
+// One workgroup: the round's slices pg[i].[base, cur), their prefix pref[0, n] and the total.
+__global__ __launch_bounds__(256) void k_pg_plan(uint32_t n, PgTake take, u64* __restrict__ pref, LkCtl* ctl) {
+  lk_block_prefix(n, pref, take);
+  if (threadIdx.x == 0) ctl->ptotal = pref[n];
+}
+
+// The round's slices as kg_query rows: ns:id#rel@subject of an object lookup's request, ns:obj#rel@id of
+// a subject lookup's.
+template <bool SUBJ, class Req>
+__global__ __launch_bounds__(256) void k_pg_rows(const PgReq* __restrict__ pg, uint32_t n, const u64* __restrict__ pref,
+                                                 const u64* __restrict__ uk, const uint32_t* __restrict__ dom,
+                                                 const Req* __restrict__ q, kg_query* cq, uint32_t* creq) {
+  const u64 total = pref[n], stride = (u64)gridDim.x * 256;
+  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
+    const uint32_t r = csr_owner((const uint64_t*)pref, n, e);
+    const PgReq& x = pg[r];
+    const u64 at = x.base + (e - pref[r]);
+    if (at >= x.hi) continue;  // never: the slice lies in the run
+    const uint32_t id = pg_cand(x, at, uk, dom);
+    const Req y = q[r];
+    kg_query z;
+    if constexpr (SUBJ) z.t = kg_tuple{y.ns, y.obj, y.rel, KG_SUBJECT_ID, id, 0};
+    else z.t = kg_tuple{y.ns, id, y.rel, y.sns, y.sobj, y.srel};
+    z.max_depth = y.max_depth;
+    cq[e] = z;
+    creq[e] = r;
+  }
+}
+
+// A subject lookup's round as keys id << 32 | request: once sorted, neighbouring checks share their subject
+// id, as the unpaged confirmation's pairs do -- the check tiers answer such a batch several times faster
+// than one whose neighbours share the object.
+constexpr u64 PG_SORT_MIN = 4096;  // smaller rounds are bound by their launches, not by the checks
+__global__ __launch_bounds__(256) void k_pg_round_keys(const PgReq* __restrict__ pg, uint32_t n,
+                                                       const u64* __restrict__ pref, const u64* __restrict__ uk,
+                                                       const uint32_t* __restrict__ dom, u64* __restrict__ keys) {
+  const u64 total = pref[n], stride = (u64)gridDim.x * 256;
+  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
+    const uint32_t r = csr_owner((const uint64_t*)pref, n, e);
+    const PgReq& x = pg[r];
+    const u64 at = min(x.base + (e - pref[r]), x.hi - 1);  // the slice lies in the run
+    keys[e] = ((u64)pg_cand(x, at, uk, dom) << 32) | r;
+  }
+}
+__global__ __launch_bounds__(256) void k_pg_key_rows(const u64* __restrict__ keys, u64 total,
+                                                     const kg_lookup_subj* __restrict__ q, uint32_t n, kg_query* cq,
+                                                     uint32_t* creq) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
+    const u64 key = keys[e];
+    const uint32_t r = min((uint32_t)key, n - 1), id = (uint32_t)(key >> 32);
+    const kg_lookup_subj y = q[r];
+    kg_query z;
+    z.t = kg_tuple{y.ns, y.obj, y.rel, KG_SUBJECT_ID, id, 0};
+    z.max_depth = y.max_depth;
+    cq[e] = z;
+    creq[e] = r;
+  }
+}
+
+// The round's answers: members join the output keys and their request's count; an erring id goes with
+// its code to the error list (ekeys: request << 32 | id).  first == 0: a rerun after the output list
+// grew -- only the output keys are written again.
+template <bool SUBJ>
+__global__ __launch_bounds__(256) void k_pg_collect(const kg_query* __restrict__ cq, const uint32_t* __restrict__ creq,
+                                                    const uint8_t* __restrict__ out, const uint32_t* __restrict__ err,
+                                                    u64 n, u64* okeys, u64 ocap, int first, PgReq* pg, u64* ekeys,
+                                                    uint32_t* ecodes, u64 ecap, LkCtl* ctl) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n; base += stride) {
+    const u64 i = base + lane_id();
+    bool mem = false, bad = false;
+    u64 key = 0;
+    uint32_t code = 0;
+    if (i < n) {
+      const uint8_t o = out[i];
+      const uint32_t r = creq[i], id = SUBJ ? cq[i].t.sobj : cq[i].t.obj;
+      mem = o == KG_IS_MEMBER;
+      key = ((u64)r << 32) | id;
+      if (first) {
+        if (mem) atomicAdd(&pg[r].nmem, 1ull);
+        bad = o == KG_ERROR;
+        code = err[i];
+      }
+    }
+    if (first) {
+      const uint64_t mm = __ballot(mem);
+      if (mm && lane_id() == 0) atomicAdd(&ctl->confirmed, (u64)__popcll(mm));
+    }
+    lk_append64(mem, key, okeys, &ctl->ocount, ocap);
+    const u64 ep = wave_reserve64(&ctl->ecount, bad ? 1u : 0u);
+    if (bad && ep < ecap) {
+      ekeys[ep] = key;
+      ecodes[ep] = code;
+    }
+  }
+}
+
+// The page of request i in the call's sorted unique output keys fk[0, m): its keys from klo[i] on that
+// lie at or below the largest candidate id it checked (all of them once its candidates ran out), the
+// first `limit` kept; next: the last kept id + 1 while a further one follows, else KG_LOOKUP_END.
+__global__ __launch_bounds__(256) void k_pg_finish(const PgReq* __restrict__ pg, uint32_t n, const u64* __restrict__ fk,
+                                                   u64 m, const u64* __restrict__ uk, const uint32_t* __restrict__ dom,
+                                                   u64* __restrict__ kept, u64* __restrict__ klo,
+                                                   uint32_t* __restrict__ next) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const PgReq x = pg[i];
+  const u64 lo = lk_lower_bound(fk, m, ((u64)i << 32) | x.from);
+  u64 hi = lk_lower_bound(fk, m, ((u64)i + 1) << 32);
+  if (x.cur < x.hi)
+    hi = x.cur > x.lo ? min(hi, lk_lower_bound(fk, m, (((u64)i << 32) | pg_cand(x, x.cur - 1, uk, dom)) + 1)) : lo;
+  hi = max(hi, lo);
+  const u64 count = hi - lo, k = min(count, (u64)x.limit);
+  kept[i] = k;
+  klo[i] = lo;
+  next[i] = count > k ? (uint32_t)fk[lo + k - 1] + 1u : KG_LOOKUP_END;
+}
+
+// The erring ids of the covered ranges [from, next): counted per request, with the code of the lowest.
+__global__ __launch_bounds__(256) void k_pg_errs(const u64* __restrict__ ekeys, const uint32_t* __restrict__ ecodes,
+                                                 u64 ne, const PgReq* __restrict__ pg, uint32_t n,
+                                                 const uint32_t* __restrict__ next, u64* n_errors, u64* errmin) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < ne; e += stride) {
+    const u64 key = ekeys[e];
+    const uint32_t r = min((uint32_t)(key >> 32), n - 1), id = (uint32_t)key, nx = next[r];
+    if (id < pg[r].from || (nx != KG_LOOKUP_END && id >= nx)) continue;
+    atomicAdd(&n_errors[r], 1ull);
+    atomicMin(&errmin[r], ((u64)id << 32) | ecodes[e]);
+  }
+}
+
+struct PgKept {
+  const u64* kept;
+  __device__ u64 operator()(uint32_t i) const { return kept[i]; }
+};
+// One workgroup: req_off[0, n] from the kept counts, and the total.
+__global__ __launch_bounds__(256) void k_pg_offsets(uint32_t n, PgKept kept, uint64_t* __restrict__ req_off, LkCtl* ctl) {
+  lk_block_prefix(n, (u64*)req_off, kept);
+  if (threadIdx.x == 0) ctl->ptotal = req_off[n];
+}
+
+// The kept ids of every page, and the error codes.
+__global__ __launch_bounds__(256) void k_pg_gather(const u64* __restrict__ fk, const u64* __restrict__ klo,
+                                                   const uint64_t* __restrict__ req_off, uint32_t n, u64 total,
+                                                   uint32_t* __restrict__ objs, const u64* __restrict__ errmin,
+                                                   uint32_t* __restrict__ err_code) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < total || i < n; i += stride) {
+    if (i < total) {
+      const uint32_t r = csr_owner(req_off, n, i);
+      objs[i] = (uint32_t)fk[klo[r] + (i - req_off[r])];
+    }
+    if (i < n) err_code[i] = errmin[i] == ~0ull ? 0u : (uint32_t)errmin[i];
+  }
+}
+
 // ------------------------------------------------------------------ host: a lane's buffers, one call
 // The device buffers of lookups on one lane, kept between calls.
 struct LookupBufs {
@@ -688,6 +957,10 @@ struct LookupBufs {
   DevBuf<u64> okeys, okeys2;
   DevBuf<uint64_t> d_off;
   DevBuf<uint32_t> d_objs, d_ecode;
+  // paged calls: the requests' pages and runs, a round's prefix, the error list, the pages' extents
+  DevBuf<PgReq> pst;
+  DevBuf<u64> ppref, ekeys, pkept, pklo, rkeys, rkeys2;
+  DevBuf<uint32_t> ecodes, d_next;
   hipEvent_t ev[2] = {};
   ~LookupBufs() {
     for (auto& e : ev)
@@ -709,6 +982,9 @@ struct Call {
   size_t n = 0;
   u64 n_exact = 0, n_cand = 0, n_conf = 0;
   uint64_t st_edges = 0, st_levels = 0;
+  // a paged call: the requests' pages (nullptr: unpaged), the rounds run, the erring keys collected
+  const kg_lookup_page* pg = nullptr;
+  u64 n_rounds = 0, n_ekeys = 0;
 
   Call(Snapshot* s_, Lane* L, int32_t gmax_)
       : s(s_), w(L->w), st(L->stream), B(*static_cast<LookupBufs*>(L->lk ? L->lk : (L->lk = new LookupBufs()))),
@@ -801,6 +1077,13 @@ struct Call {
 
   // The end: the keys sorted, duplicates dropped, split by request, the output arrays in one pinned block.
   int finish(kg_lookup_buf* out);
+  // the m ids of B.d_objs with B.d_off / n_errors / d_ecode (and d_next: a paged call's next[n]) copied
+  // into one pinned block; the call's counters
+  int deliver(kg_lookup_buf* out, u64 m, uint32_t** next);
+  // a paged call: the requests' pages on the device (implicit[i]: request i's candidates are the domain)
+  int page_upload(const std::vector<uint8_t>& implicit);
+  // the end of a paged call: every request's page cut out of the sorted unique keys
+  int finish_page(kg_lookup_pages* out, const u64* uk, const uint32_t* dom);
 };
 
 // keys a[0, n) sorted over their bits [0, end_bit): *out (in a or b); with n_uniq, one of each.
@@ -843,19 +1126,25 @@ int Call::finish(kg_lookup_buf* out) {
                      0, st, uk, m, (uint32_t)n, B.d_off.get(), B.d_objs.get(), (const u64*)B.errmin.get(),
                      B.d_ecode.get());
   HIPC(hipGetLastError());
-  // one pinned block: req_off[n + 1] | n_errors[n] | objs[m] | err_code[n]
-  const size_t bytes = ((size_t)n + 1) * 8 + (size_t)n * 8 + (size_t)m * 4 + (size_t)n * 4;
+  return deliver(out, m, nullptr);
+}
+
+int Call::deliver(kg_lookup_buf* out, u64 m, uint32_t** next) {
+  // one pinned block: req_off[n + 1] | n_errors[n] | objs[m] | err_code[n] | next[n] (a paged call)
+  const size_t bytes = ((size_t)n + 1) * 8 + (size_t)n * 8 + (size_t)m * 4 + (size_t)n * 4 + (next ? (size_t)n * 4 : 0);
   char* blk = (char*)tree_pool_get(bytes);
   if (!blk) return set_error(KG_ERR_RESOURCE_CODE, "lookup: pinned output allocation failed");
   uint64_t* o_off = (uint64_t*)blk;
   uint64_t* o_nerr = o_off + n + 1;
   uint32_t* o_objs = (uint32_t*)(o_nerr + n);
   uint32_t* o_ecode = o_objs + m;
+  uint32_t* o_next = o_ecode + n;
   int rc = 0;
   if (hipMemcpyAsync(o_off, B.d_off.get(), (n + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(o_nerr, B.n_errors.get(), n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
       (m && hipMemcpyAsync(o_objs, B.d_objs.get(), (size_t)m * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
       hipMemcpyAsync(o_ecode, B.d_ecode.get(), n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      (next && hipMemcpyAsync(o_next, B.d_next.get(), n * 4, hipMemcpyDeviceToHost, st) != hipSuccess) ||
       hipEventRecord(B.ev[1], st) != hipSuccess)
     rc = set_error(-1, "lookup: D2H copy failed");
   if (!rc) rc = w->wait(st, true);
@@ -882,6 +1171,7 @@ int Call::finish(kg_lookup_buf* out) {
   out->confirmed = n_conf;
   out->reverse_edges = st_edges;
   out->levels = st_levels;
+  if (next) *next = o_next;
   return 0;
 }
 
@@ -922,6 +1212,141 @@ int keep_grow(Call& c, DevBuf<T>& buf, size_t keep, size_t need) {
   if (keep) HIPC(hipMemcpyAsync(nb.get(), buf.get(), keep * sizeof(T), hipMemcpyDeviceToDevice, c.st));
   HIPC(hipStreamSynchronize(c.st));
   buf = std::move(nb);
+  return 0;
+}
+
+// ------------------------------------------------------------------ host: a paged call
+int Call::page_upload(const std::vector<uint8_t>& implicit) {
+  std::vector<PgReq> h(n);
+  for (size_t i = 0; i < n; i++) h[i] = PgReq{0, 0, 0, 0, 0, pg[i].from, pg[i].limit, implicit.empty() ? 0u : implicit[i], 0};
+  HIPC(B.pst.reserve(n));
+  HIPC(hipMemcpyAsync(B.pst.get(), h.data(), n * sizeof(PgReq), hipMemcpyHostToDevice, st));
+  HIPC(hipStreamSynchronize(st));  // h is pageable
+  return 0;
+}
+
+// A round's answers collected (k_pg_collect); the output list grows like collect()'s.
+template <bool SUBJ>
+int collect_page(Call& c, u64 total) {
+  LookupBufs& B = c.B;
+  for (int pass = 0;; pass++) {
+    hipLaunchKernelGGL(k_pg_collect<SUBJ>, dim3((uint32_t)std::min<u64>(c.grid_wide, total / 256 + 1)), dim3(256), 0, c.st,
+                       (const kg_query*)B.cq.get(), (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(),
+                       (const uint32_t*)B.cerr.get(), total, B.okeys.get(), c.O.cap, pass == 0 ? 1 : 0, B.pst.get(),
+                       B.ekeys.get(), B.ecodes.get(), (u64)std::min(B.ekeys.cap(), B.ecodes.cap()), B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    bool again = false;
+    if (int rc = c.settle(h, &again)) return rc;
+    if (again) {
+      if (pass) return set_error(KG_ERR_RESOURCE_CODE, "lookup: output list overflowed twice");
+      continue;
+    }
+    c.n_conf = h.confirmed;
+    c.n_ekeys = h.ecount;
+    return 0;
+  }
+}
+
+// The confirmation of a paged call in ascending rounds.  uk[0, m): the call's sorted unique candidate
+// keys; dom[0, n_dom): the domain of the implicit requests (any_implicit: there is one).  A call without
+// candidates takes no round.
+template <bool SUBJ, class Req>
+int page_rounds(Call& c, const u64* uk, u64 m, const uint32_t* dom, u64 n_dom, bool any_implicit) {
+  LookupBufs& B = c.B;
+  const uint32_t n = (uint32_t)c.n, blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_pg_init, dim3(blocks), dim3(256), 0, c.st, B.pst.get(), n, uk, m, dom, n_dom);
+  HIPC(hipGetLastError());
+  if (!m && !(any_implicit && n_dom)) return 0;
+  // the walk's keys sorted, one of each, at the head of B.okeys: a round counts a request's keys below an id
+  if (c.O.have) {
+    HIPC(B.okeys2.reserve((size_t)c.O.cap));
+    const u64* xk = nullptr;
+    u64 mx = 0;
+    if (int rc = sort_keys(c, B.okeys, B.okeys2, (size_t)c.O.have, key_bits(c.n), &xk, &mx)) return rc;
+    if (xk != B.okeys.get()) std::swap(B.okeys, B.okeys2);
+    c.O.have = mx;
+    if (int rc = c.rewind()) return rc;
+  }
+  const u64 mx = c.O.have;
+  HIPC(B.ppref.reserve((size_t)n + 1));
+  for (;;) {
+    // B.okeys may have grown: its head is read through the current pointer
+    hipLaunchKernelGGL(k_pg_plan, dim3(1), dim3(256), 0, c.st, n, PgTake{B.pst.get(), uk, dom, B.okeys.get(), mx},
+                       B.ppref.get(), B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    const u64 total = h.ptotal;
+    if (!total) return 0;
+    c.n_rounds++;
+    HIPC(B.cq.reserve((size_t)total));
+    HIPC(B.creq.reserve((size_t)total));
+    HIPC(B.cout.reserve((size_t)total));
+    HIPC(B.cerr.reserve((size_t)total));
+    if (int rc = keep_grow(c, B.ekeys, (size_t)c.n_ekeys, (size_t)(c.n_ekeys + total))) return rc;
+    if (int rc = keep_grow(c, B.ecodes, (size_t)c.n_ekeys, (size_t)(c.n_ekeys + total))) return rc;
+    const dim3 rgrid((uint32_t)std::min<u64>(c.grid_wide, total / 256 + 1));
+    bool by_subject = false;
+    if constexpr (SUBJ) {
+      if (total >= PG_SORT_MIN) {  // the round's checks ordered by subject id
+        by_subject = true;
+        HIPC(B.rkeys.reserve((size_t)total));
+        hipLaunchKernelGGL(k_pg_round_keys, rgrid, dim3(256), 0, c.st, (const PgReq*)B.pst.get(), n,
+                           (const u64*)B.ppref.get(), uk, dom, B.rkeys.get());
+        HIPC(hipGetLastError());
+        const u64* sk = nullptr;
+        if (int rc = sort_keys(c, B.rkeys, B.rkeys2, (size_t)total, 64, &sk, (u64*)nullptr)) return rc;
+        hipLaunchKernelGGL(k_pg_key_rows, rgrid, dim3(256), 0, c.st, sk, total, (const kg_lookup_subj*)B.d_req.get(), n,
+                           B.cq.get(), B.creq.get());
+      }
+    }
+    if (!by_subject)
+      hipLaunchKernelGGL((k_pg_rows<SUBJ, Req>), rgrid, dim3(256), 0, c.st, (const PgReq*)B.pst.get(), n,
+                         (const u64*)B.ppref.get(), uk, dom, (const Req*)B.d_req.get(), B.cq.get(), B.creq.get());
+    HIPC(hipGetLastError());
+    constexpr u64 CHUNK = 1ull << 26;
+    for (u64 at = 0; at < total; at += CHUNK) {
+      const size_t k = (size_t)std::min(CHUNK, total - at);
+      if (int rc = check_batch_device(c.s, c.w, B.cq.get() + at, k, c.gmax, B.cout.get() + at, B.cerr.get() + at, nullptr))
+        return rc;
+    }
+    if (int rc = collect_page<SUBJ>(c, total)) return rc;
+    c.n_cand += total;
+  }
+}
+
+int Call::finish_page(kg_lookup_pages* out, const u64* uk, const uint32_t* dom) {
+  u64 m = 0;
+  const u64* fk = B.okeys.get();
+  if (O.have)
+    if (int rc = sort_keys(*this, B.okeys, B.okeys2, (size_t)O.have, key_bits(n), &fk, &m)) return rc;
+  const uint32_t nr = (uint32_t)n, blocks = (nr + 255) / 256;
+  HIPC(B.pkept.reserve(n));
+  HIPC(B.pklo.reserve(n));
+  HIPC(B.d_next.reserve(n));
+  HIPC(B.d_off.reserve(n + 1));
+  HIPC(B.d_ecode.reserve(n));
+  hipLaunchKernelGGL(k_pg_finish, dim3(blocks), dim3(256), 0, st, (const PgReq*)B.pst.get(), nr, fk, m, uk, dom,
+                     B.pkept.get(), B.pklo.get(), B.d_next.get());
+  if (n_ekeys)
+    hipLaunchKernelGGL(k_pg_errs, dim3((uint32_t)std::min<u64>(grid_wide, n_ekeys / 256 + 1)), dim3(256), 0, st,
+                       (const u64*)B.ekeys.get(), (const uint32_t*)B.ecodes.get(), n_ekeys, (const PgReq*)B.pst.get(), nr,
+                       (const uint32_t*)B.d_next.get(), B.n_errors.get(), B.errmin.get());
+  hipLaunchKernelGGL(k_pg_offsets, dim3(1), dim3(256), 0, st, nr, PgKept{B.pkept.get()}, B.d_off.get(), B.ctl.get());
+  HIPC(hipGetLastError());
+  LkCtl h;
+  if (int rc = read_ctl(&h)) return rc;
+  const u64 total = std::min(h.ptotal, m);
+  HIPC(B.d_objs.reserve((size_t)std::max<u64>(total, 1)));
+  hipLaunchKernelGGL(k_pg_gather, dim3((uint32_t)std::min<u64>(grid_wide, std::max<u64>(total, n) / 256 + 1)), dim3(256), 0,
+                     st, fk, (const u64*)B.pklo.get(), (const uint64_t*)B.d_off.get(), nr, total, B.d_objs.get(),
+                     (const u64*)B.errmin.get(), B.d_ecode.get());
+  HIPC(hipGetLastError());
+  if (int rc = deliver(&out->list, total, &out->next)) return rc;
+  out->rounds = n_rounds;
+  out->pinned = out->list.pinned;
   return 0;
 }
 
@@ -1064,7 +1489,7 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
     for (uint32_t b = 0; b < gn; b++)
       if (dir.formula(greq[g0 + b].req)) fmask |= 1ull << b;
     Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), c.O.cap,
-           fmask, B.kkeys.get(), c.K.cap, B.greq.get() + g0, B.ctl.get()};
+           fmask, B.kkeys.get(), c.K.cap, B.greq.get() + g0, B.ctl.get(), c.pg != nullptr};
     B.dirty = true;
     LkCtl h;
     uint32_t cur = 0, F = 0;
@@ -1112,9 +1537,13 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
 
 void lookup_bufs_free(void* p) { delete static_cast<LookupBufs*>(p); }
 
-// kg_lookup_objects on lane L (its stream and workspace; the caller holds the workspace's mutex).
-int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+// kg_lookup_objects on lane L (its stream and workspace; the caller holds the workspace's mutex).  pages:
+// kg_lookup_objects_page -- the same steps, with the candidates as keys checked in rounds, into pout.
+static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n, int32_t gmax,
+                      kg_lookup_buf* out, kg_lookup_pages* pout) {
   Call c(s, L, gmax);
+  c.pg = pages;
+  const bool paged = pages != nullptr;
   LookupBufs& B = c.B;
   hipStream_t st = c.st;
   const DevSnap& ds = s->ds;
@@ -1153,7 +1582,11 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
     // candidates of a reverse request: impure nodes -- none without node flags
     if (lr[i].mode == LK_NODES || ds.nflags) by_key[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
   }
-  if (!by_fkey.empty())
+  if (paged) {
+    for (GReq& g : greq) g.from = pages[g.req].from;
+    if (int rc = c.page_upload({})) return rc;
+  }
+  if (!by_fkey.empty() || (paged && (!by_key.empty() || !by_ns.empty())))
     if (int rc = c.want_cand_keys()) return rc;
   if (int rc = walk_groups(c, greq, ReverseWalk{lr})) return rc;
 
@@ -1208,11 +1641,16 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
       HIPC(B.creq.reserve((size_t)ccap));
       if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
       HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, st));  // ccount, dcount
-      if (FK)  // the candidate keys back at the walk's
+      if (FK || paged)  // the candidate keys back at the walk's
         if (int rc = c.rewind()) return rc;
-      hipLaunchKernelGGL(k_lk_scan, dim3(std::max(1u, std::min(c.grid_wide, ds.n_nodes / 256 + 1))), dim3(256), 0, st, ds,
-                         T, d_req, B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap,
-                         B.ctl.get());
+      const dim3 sgrid(std::max(1u, std::min(c.grid_wide, ds.n_nodes / 256 + 1)));
+      const PgReq* d_pg = B.pst.get();
+      if (paged)
+        hipLaunchKernelGGL(k_lk_scan<true>, sgrid, dim3(256), 0, st, ds, T, d_req, B.cq.get(), B.creq.get(), ccap,
+                           B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
+      else
+        hipLaunchKernelGGL(k_lk_scan<false>, sgrid, dim3(256), 0, st, ds, T, d_req, B.cq.get(), B.creq.get(), ccap,
+                           B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
       HIPC(hipGetLastError());
       LkCtl h;
       if (int rc = c.read_ctl(&h)) return rc;
@@ -1227,8 +1665,13 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
         const size_t nd = (size_t)h.dcount;
         const u64* dk = nullptr;
         if (int rc = sort_keys(c, B.dkeys, B.dkeys2, nd, 64, &dk, (u64*)nullptr)) return rc;
-        hipLaunchKernelGGL(k_lk_domain, dim3((uint32_t)std::min<u64>(c.grid_wide, nd / 256 + 1)), dim3(256), 0, st, T,
-                           dk, (u64)nd, d_req, B.cq.get(), B.creq.get(), ccap, B.ctl.get());
+        const dim3 dgrid((uint32_t)std::min<u64>(c.grid_wide, nd / 256 + 1));
+        if (paged)
+          hipLaunchKernelGGL(k_lk_domain<true>, dgrid, dim3(256), 0, st, T, dk, (u64)nd, d_req, B.cq.get(), B.creq.get(),
+                             ccap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
+        else
+          hipLaunchKernelGGL(k_lk_domain<false>, dgrid, dim3(256), 0, st, T, dk, (u64)nd, d_req, B.cq.get(), B.creq.get(),
+                             ccap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
         HIPC(hipGetLastError());
         if (int rc = c.read_ctl(&h)) return rc;
       }
@@ -1236,10 +1679,23 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
         ccap = h.ccount;
         continue;
       }
+      if (h.kcount > c.K.cap) {  // a paged call: the domain's keys did not fit
+        if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
+        continue;
+      }
       c.n_cand = h.ccount;
       c.K.have = h.kcount;
       break;
     }
+  }
+  // ---- a paged call: every candidate is a key; one of each, checked in ascending rounds
+  if (paged) {
+    const u64* uk = nullptr;
+    u64 m = 0;
+    if (c.K.have)
+      if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
+    if (int rc = (page_rounds<false, kg_lookup>(c, uk, m, nullptr, 0, false))) return rc;
+    return c.finish_page(pout, uk, nullptr);
   }
   // ---- the formula requests' candidate keys, one of each, as checks behind the others
   if (c.K.have) {
@@ -1271,8 +1727,11 @@ int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_
 // kg_lookup_subjects on lane L (as lookup_objects).  Walk-mode requests are listed by the forward walk,
 // 64 bits per group; formula-mode requests take a bit per walk-leaf root there, and what those list is
 // checked; the others by a check of every subject id of the domain, in chunks of CHUNK pairs.
-int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+                       int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
   Call c(s, L, gmax);
+  c.pg = pages;
+  const bool paged = pages != nullptr;
   LookupBufs& B = c.B;
   hipStream_t st = c.st;
   const DevSnap& ds = s->ds;
@@ -1299,6 +1758,12 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
           any_formula = true;
         }
     } else if (sr[i].mode == LS_CONFIRM) conf.push_back((uint32_t)i);
+  }
+  if (paged) {
+    std::vector<uint8_t> implicit(n, 0);
+    for (uint32_t r : conf) implicit[r] = 1;
+    for (GReq& g : greq) g.from = pages[g.req].from;
+    if (int rc = c.page_upload(implicit)) return rc;
   }
   if (any_formula)
     if (int rc = c.want_cand_keys()) return rc;
@@ -1332,6 +1797,19 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
     dom = B.dom.get();
     if (!bits && n_dom)  // an id per row entry that holds it: sort, one of each
       if (int rc = sort_keys(c, B.dom, B.dom2, (size_t)n_dom, 31, &dom, &n_dom)) return rc;
+    // the bitmap's ids are distinct but come in the order its waves reserved their entries: a paged call
+    // indexes the domain by id
+    if (bits && n_dom && paged)
+      if (int rc = sort_keys(c, B.dom, B.dom2, (size_t)n_dom, 32, &dom, (u64*)nullptr)) return rc;
+  }
+  // ---- a paged call: the confirm requests index the domain, the formula requests their unique keys
+  if (paged) {
+    const u64* uk = nullptr;
+    u64 m = 0;
+    if (c.K.have)
+      if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
+    if (int rc = (page_rounds<true, kg_lookup_subj>(c, uk, m, dom, n_dom, !conf.empty()))) return rc;
+    return c.finish_page(pout, uk, dom);
   }
   if (n_dom) {
     const uint32_t C = (uint32_t)conf.size();
@@ -1378,6 +1856,21 @@ int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, 
     }
   }
   return c.finish(out);
+}
+
+int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+  return lookup_objects_on(s, L, reqs, nullptr, n, gmax, out, nullptr);
+}
+int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+  return lookup_subjects_on(s, L, reqs, nullptr, n, gmax, out, nullptr);
+}
+int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n, int32_t gmax,
+                        kg_lookup_pages* out) {
+  return lookup_objects_on(s, L, reqs, pages, n, gmax, &out->list, out);
+}
+int lookup_subjects_page(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+                         int32_t gmax, kg_lookup_pages* out) {
+  return lookup_subjects_on(s, L, reqs, pages, n, gmax, &out->list, out);
 }
 
 void lookup_free(kg_lookup_buf* out) {

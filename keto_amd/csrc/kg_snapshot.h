@@ -486,6 +486,11 @@ void tree_pool_put(void* p, size_t bytes);
 int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t global_max_depth, kg_lookup_buf* out);
 int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
                     kg_lookup_buf* out);
+// the paged calls (pages[n]: every limit >= 1): out->list, out->next (in list's block) and out->rounds
+int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n,
+                        int32_t global_max_depth, kg_lookup_pages* out);
+int lookup_subjects_page(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+                         int32_t global_max_depth, kg_lookup_pages* out);
 void lookup_free(kg_lookup_buf* out);
 void lookup_bufs_free(void* bufs);
 // kg_query.hip: kg_snapshot_query on lane L (the caller holds L->w->mu); query_free returns its output

@@ -467,6 +467,77 @@ class Engine:
             raise CheckError(int(err[0]))
         return sorted(it.obj_name(int(i)) for i in ids)
 
+    # ---- paged lookups: the next `limit` ids from a cursor (kg_lookup_objects_page / kg_lookup_subjects_page)
+    def lookup_objects_page_ids(self, reqs: np.ndarray, pages: np.ndarray, with_stats: bool = False):
+        """reqs as lookup_objects_ids; pages: (n,2) uint32 (from, limit >= 1).  Returns (req_off, objs, err_code,
+        n_errors, next): request i's page is the first `limit` ids >= `from` of its unpaged answer; next[i] is
+        the next call's `from` or KG_LOOKUP_END; err_code / n_errors are about the ids in [from, next).
+        last_stats additionally carries `rounds`."""
+        return self._lookup_page("kg_lookup_objects_page", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6), pages,
+                                 with_stats)
+
+    def lookup_subjects_page_ids(self, reqs: np.ndarray, pages: np.ndarray, with_stats: bool = False):
+        """reqs as lookup_subjects_ids; pages and the result as lookup_objects_page_ids."""
+        return self._lookup_page("kg_lookup_subjects_page", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 4), pages,
+                                 with_stats)
+
+    def _lookup_page(self, call: str, reqs: np.ndarray, pages: np.ndarray, with_stats: bool):
+        n = reqs.shape[0]
+        pages = np.ascontiguousarray(pages, np.uint32).reshape(-1, 2)
+        if pages.shape[0] != n:
+            raise ValueError("one page per request")
+        out = _lib.kg_lookup_pages()
+        L = _lib.load()
+        _lib.check(getattr(L, call)(self.snapshot.handle, _ptr(reqs) if n else None, _ptr(pages) if n else None, n,
+                                    self.config.max_read_depth, C.byref(out)), call)
+        try:
+            buf = out.list
+            m = int(buf.n_objs)
+            off = np.ctypeslib.as_array(buf.req_off, shape=(n + 1,)).copy()
+            objs = np.ctypeslib.as_array(buf.objs, shape=(m,)).copy() if m else np.zeros(0, np.uint32)
+            err = np.ctypeslib.as_array(buf.err_code, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+            nerr = np.ctypeslib.as_array(buf.n_errors, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            nxt = np.ctypeslib.as_array(out.next, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+            if with_stats:
+                self.last_stats = {k: getattr(buf, k) for k in ("n_objs", "exact", "candidates", "confirmed",
+                                                                "reverse_edges", "levels", "kernel_ms")}
+                self.last_stats["rounds"] = int(out.rounds)
+            else:
+                self.last_stats = None
+        finally:
+            L.kg_lookup_pages_free(C.byref(out))
+        return off, objs, err, nerr, nxt
+
+    def _page_names(self, objs, err, nerr, nxt) -> Tuple[List[str], Optional[int]]:
+        if int(nerr[0]):
+            raise CheckError(int(err[0]))
+        it = self.snapshot.interner
+        return [it.obj_name(int(o)) for o in objs], None if int(nxt[0]) == _lib.KG_LOOKUP_END else int(nxt[0])
+
+    def lookup_objects_page(self, namespace: str, relation: str, subject, rest_depth: int, frm: int = 0,
+                            limit: int = 100) -> Tuple[List[str], Optional[int]]:
+        """One page of lookup_objects in id order: (the names of the first `limit` objects with id >= frm, the
+        next page's frm or None at the end).  Raises CheckError only when an object of the page's id range
+        [frm, next) ends in an error."""
+        it = self.snapshot.interner
+        if isinstance(subject, SubjectSet):
+            sub = list(it.subject_set_ids(subject))
+        else:
+            sub = [SUBJECT_ID, it.obj_id(subject), 0]
+        row = np.asarray([it.ns_id(namespace), it.rel_id(relation), *sub, np.int32(rest_depth).view(np.uint32)],
+                         np.uint32)
+        _, objs, err, nerr, nxt = self.lookup_objects_page_ids(row, np.asarray([[frm, limit]], np.uint32))
+        return self._page_names(objs, err, nerr, nxt)
+
+    def lookup_subjects_page(self, namespace: str, object: str, relation: str, rest_depth: int, frm: int = 0,
+                             limit: int = 100) -> Tuple[List[str], Optional[int]]:
+        """One page of lookup_subjects in id order, as lookup_objects_page."""
+        it = self.snapshot.interner
+        row = np.asarray([it.ns_id(namespace), it.obj_id(object), it.rel_id(relation),
+                          np.int32(rest_depth).view(np.uint32)], np.uint32)
+        _, ids, err, nerr, nxt = self.lookup_subjects_page_ids(row, np.asarray([[frm, limit]], np.uint32))
+        return self._page_names(ids, err, nerr, nxt)
+
 
 class ExpandEngine:
     """expand.Engine: subject-set trees."""

@@ -258,9 +258,29 @@ class ExpandHandler:
         return {"tree": tree.to_json()}
 
 
+def parse_id_page(order: str, page_token: str, page_size: int) -> Optional[Tuple[int, int]]:
+    """The page of a list request with order=id: (from, limit) for the paged lookup -- the token is the
+    decimal id to start from (empty: 0).  None: no order given, the name-ordered paging.  A malformed
+    token, size or order is the 400 of the name-ordered paging."""
+    if not order:
+        return None
+    try:
+        if order != "id":
+            raise ValueError
+        if page_token and not (page_token.isascii() and page_token.isdigit()):
+            raise ValueError
+        frm = int(page_token) if page_token else 0
+        if frm > 0xFFFFFFFF or not 1 <= page_size <= 0xFFFFFFFF:
+            raise ValueError
+    except ValueError:
+        raise _bad("malformed page_token or page_size")
+    return frm, page_size
+
+
 class ListObjectsHandler:
     """Reverse lookup over one engine (no reference counterpart; OpenFGA ListObjects' shape): the objects of
-    a namespace on which a subject has a relation, in name order, paged."""
+    a namespace on which a subject has a relation, in name order, paged -- or, with order=id, in id order
+    through the paged lookup: the page token is the id to go on from, and only the page is computed."""
 
     DEFAULT_PAGE_SIZE = 100
 
@@ -268,7 +288,7 @@ class ListObjectsHandler:
         self.engine, self.mapper = engine, mapper
 
     def _list(self, namespace: str, relation: str, sid: Optional[str], sset: Optional[SubjectSet], max_depth: int,
-              page_size: int, page_token: str) -> dict:
+              page_size: int, page_token: str, order: str = "") -> dict:
         if sid is None and sset is None:
             raise _bad(ERR_NIL_SUBJECT)
         try:  # the namespaces of the request as the check's mapper sees them
@@ -277,6 +297,14 @@ class ListObjectsHandler:
                 self.mapper.check_namespace(sset.namespace)
         except NamespaceNotFound as e:
             raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        by_id = parse_id_page(order, page_token, page_size)
+        if by_id is not None:
+            try:
+                names, nxt = self.engine.lookup_objects_page(namespace, relation, sset if sset is not None else sid,
+                                                             max_depth, by_id[0], by_id[1])
+            except CheckError as e:
+                raise HandlerError(500, str(e))
+            return {"objects": names, "next_page_token": "" if nxt is None else str(nxt)}
         try:
             at = int(page_token) if page_token else 0
             if at < 0 or page_size < 1:
@@ -291,7 +319,7 @@ class ListObjectsHandler:
         return {"objects": page, "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
 
     def get_list_objects(self, query: Union[str, Query]) -> Tuple[int, dict]:
-        """GET ?namespace=&relation=&subject_id= | subject_set.*=&max-depth=&page_size=&page_token=."""
+        """GET ?namespace=&relation=&subject_id= | subject_set.*=&max-depth=&page_size=&page_token=&order=."""
         try:
             q = parse_query(query)
             d = max_depth_from_query(q)
@@ -302,13 +330,14 @@ class ListObjectsHandler:
                 size = parse_go_int(_get(q, "page_size")) if "page_size" in q else self.DEFAULT_PAGE_SIZE
             except ValueError:
                 raise _bad("malformed page_token or page_size")
-            return 200, self._list(_get(q, "namespace"), _get(q, "relation"), sid, sset, d, size, _get(q, "page_token"))
+            return 200, self._list(_get(q, "namespace"), _get(q, "relation"), sid, sset, d, size, _get(q, "page_token"),
+                                   _get(q, "order"))
         except HandlerError as e:
             return e.status, e.body()
 
     def grpc_list_objects(self, req: dict) -> dict:
         """req = {"namespace", "relation", "subject": {"id"} | {"set": {...}}, "max_depth", "page_size",
-        "page_token"}.  Raises HandlerError (grpc_code) on failure."""
+        "page_token", "order"}.  Raises HandlerError (grpc_code) on failure."""
         sub = req.get("subject")
         if not sub:
             raise _bad(ERR_NIL_SUBJECT)
@@ -319,12 +348,14 @@ class ListObjectsHandler:
             s = sub.get("set") or {}
             sset = SubjectSet(s.get("namespace", ""), s.get("object", ""), s.get("relation", ""))
         return self._list(req.get("namespace", ""), req.get("relation", ""), sid, sset, int(req.get("max_depth", 0)),
-                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))
+                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")),
+                          str(req.get("order", "")))
 
 
 class ListSubjectsHandler:
     """Subject lookup over one engine (no reference counterpart; OpenFGA ListUsers' shape): the subject ids
-    that have a relation on an object, in name order, paged like ListObjectsHandler."""
+    that have a relation on an object, in name order -- or id order with order=id -- paged like
+    ListObjectsHandler."""
 
     DEFAULT_PAGE_SIZE = ListObjectsHandler.DEFAULT_PAGE_SIZE
 
@@ -332,11 +363,18 @@ class ListSubjectsHandler:
         self.engine, self.mapper = engine, mapper
 
     def _list(self, namespace: str, object: str, relation: str, max_depth: int, page_size: int,
-              page_token: str) -> dict:
+              page_token: str, order: str = "") -> dict:
         try:
             self.mapper.check_namespace(namespace)
         except NamespaceNotFound as e:
             raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        by_id = parse_id_page(order, page_token, page_size)
+        if by_id is not None:
+            try:
+                names, nxt = self.engine.lookup_subjects_page(namespace, object, relation, max_depth, by_id[0], by_id[1])
+            except CheckError as e:
+                raise HandlerError(500, str(e))
+            return {"subject_ids": names, "next_page_token": "" if nxt is None else str(nxt)}
         try:
             at = int(page_token) if page_token else 0
             if at < 0 or page_size < 1:
@@ -351,7 +389,7 @@ class ListSubjectsHandler:
         return {"subject_ids": page, "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
 
     def get_list_subjects(self, query: Union[str, Query]) -> Tuple[int, dict]:
-        """GET ?namespace=&object=&relation=&max-depth=&page_size=&page_token=."""
+        """GET ?namespace=&object=&relation=&max-depth=&page_size=&page_token=&order=."""
         try:
             q = parse_query(query)
             d = max_depth_from_query(q)
@@ -362,18 +400,19 @@ class ListSubjectsHandler:
             except ValueError:
                 raise _bad("malformed page_token or page_size")
             return 200, self._list(_get(q, "namespace"), _get(q, "object"), _get(q, "relation"), d, size,
-                                   _get(q, "page_token"))
+                                   _get(q, "page_token"), _get(q, "order"))
         except HandlerError as e:
             return e.status, e.body()
 
     def grpc_list_subjects(self, req: dict) -> dict:
-        """req = {"namespace", "object", "relation", "max_depth", "page_size", "page_token"}.  Raises
+        """req = {"namespace", "object", "relation", "max_depth", "page_size", "page_token", "order"}.  Raises
         HandlerError (grpc_code) on failure."""
         for k in ("namespace", "object", "relation"):
             if not req.get(k):
                 raise _bad('incomplete request, provide "namespace", "object" and "relation"')
         return self._list(req["namespace"], req["object"], req["relation"], int(req.get("max_depth", 0)),
-                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")))
+                          int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")),
+                          str(req.get("order", "")))
 
 
 def relation_query_from_url_query(q: dict):

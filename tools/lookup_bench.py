@@ -3,7 +3,7 @@ and for a batch of 64, and for the same requests every object of the namespace t
 kg_check_batch_device (queries resident in HBM, so the brute force pays no host transfer).
 
   python tools/lookup_bench.py [--mode objects|subjects] [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
-                               [--preset 0|1] [--relation NAME]
+                               [--preset 0|1] [--relation NAME] [--page N]
 
 --mode subjects measures the mirror image the same way: kg_lookup_subjects for one doc and for 64 docs
 against every subject id of the snapshot's tuples through kg_check_batch_device.
@@ -17,6 +17,13 @@ view gives the number of doc#view members of the same subjects: what a share req
 
 Prints one JSON line: median wall-clock milliseconds of both paths, their ratio, and the lookup call's
 reverse_edges / levels / n_objs.  The two answers are compared before anything is timed.
+
+--page N times the paged call (kg_lookup_objects_page / kg_lookup_subjects_page: the first N ids of every
+request) against what a caller did before it, the unpaged call plus a slice on the host, for one request and
+for 64, in every mode the other options select (--preset 0: the walk; --preset 1: "lookup_formula" 1 and
+0).  The page is compared with the slice of the unpaged answer before anything is timed; no brute force is
+run.  Each entry carries the paged call's candidates, rounds and n_objs beside the unpaged call's.  A library
+without the paged calls (an older build through KG_LIB_PATH) is timed for the unpaged call and the slice alone.
 """
 import argparse
 import ctypes as C
@@ -42,6 +49,7 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--preset", type=int, choices=(0, 1), default=0)
     ap.add_argument("--relation", default=None, help="default: viewer (preset 0), share (preset 1)")
+    ap.add_argument("--page", type=int, default=0, help="time the paged call for the first N ids against unpaged + slice")
     a = ap.parse_args(argv)
     import torch
     from keto_amd import _lib
@@ -85,6 +93,12 @@ def main(argv=None):
         out = {"gpu": out["gpu"], "preset": a.preset, "relation": relation, "tuples": out["tuples"], "nodes": out["nodes"],
                "domain_subject_ids": int(len(domain)),
                "depth": a.depth, "check_row_of_doc": int(rlen[mid[32]])}
+    if a.page:
+        out["page"] = a.page
+        for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
+            out[name] = page_entry(a, eng, snap, keys, reqs, hasattr(L, "kg_lookup_objects_page"))
+        print(json.dumps(out))
+        return
     stream = torch.cuda.current_stream(dev)
     for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
         n = len(reqs)
@@ -142,6 +156,51 @@ def main(argv=None):
             out[name]["lookup_formula"] = by_key
         del q, dq, d_out, d_err
     print(json.dumps(out))
+
+
+def page_entry(a, eng, snap, keys, reqs, have_paged):
+    """--page: per value of "lookup_formula" the medians of the paged call and of the unpaged call plus the
+    host slice, with both calls' counters."""
+    n = len(reqs)
+    pages = np.stack([np.zeros(n, np.uint32), np.full(n, a.page, np.uint32)], 1)
+    unpaged = eng.lookup_subjects_ids if a.mode == "subjects" else eng.lookup_objects_ids
+    paged = eng.lookup_subjects_page_ids if a.mode == "subjects" else eng.lookup_objects_page_ids
+
+    def median_ms(fn):
+        xs = []
+        for k in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            fn()
+            if k >= a.warmup:
+                xs.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(xs)
+
+    def sliced():
+        off, objs, err, nerr = unpaged(reqs, with_stats=True)
+        return [objs[int(off[i]):int(off[i + 1])][:a.page] for i in range(n)], off
+
+    entry = {"requests": n}
+    for key in keys:
+        if key is not None:
+            snap.tune("lookup_formula", key)
+        want, off = sliced()
+        st = eng.last_stats
+        e = {"unpaged_slice_ms": None, "unpaged_n_objs": int(st["n_objs"]), "unpaged_candidates": int(st["candidates"]),
+             "unpaged_exact": int(st["exact"])}
+        if have_paged:
+            poff, ids, err, nerr, nxt = paged(reqs, pages, with_stats=True)
+            for i in range(n):  # the page is the slice, before anything is timed
+                assert np.array_equal(ids[int(poff[i]):int(poff[i + 1])], want[i]), (key, i)
+                assert (int(nxt[i]) == 0xFFFFFFFF) == (int(off[i + 1] - off[i]) <= a.page), (key, i)
+            e["page_ms"] = round(median_ms(lambda: paged(reqs, pages, with_stats=True)), 4)
+            st = eng.last_stats
+            e.update({"page_kernel_ms": round(st["kernel_ms"], 4), "n_objs": int(st["n_objs"]), "exact": int(st["exact"]),
+                      "candidates": int(st["candidates"]), "confirmed": int(st["confirmed"]), "rounds": int(st["rounds"])})
+        e["unpaged_slice_ms"] = round(median_ms(sliced), 4)
+        if have_paged:
+            e["unpaged_over_page"] = round(e["unpaged_slice_ms"] / e["page_ms"], 2)
+        entry[str(key)] = e
+    return entry
 
 
 if __name__ == "__main__":
