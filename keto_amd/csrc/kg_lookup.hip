@@ -27,7 +27,10 @@
 // nodes walks from its J-leaf roots: the ids they list are its candidates (an id none of them lists is
 // NotMember of every J leaf, so of f), made unique and confirmed.  Everything else confirms every
 // subject id.  "Confirmed" = run through check_batch_device as kg_query rows built on the device; no
-// check kernel is touched.
+// check kernel is touched.  Every confirmation -- the object lookup's candidates, the subject lookup's
+// (subject id, request) pairs, either's formula keys, a paged round -- is one call of confirm(): a launch that
+// builds the rows (all of them through lk_row), the checks in chunks, one collect (k_lk_collect; where the
+// errors go is its sink: counted per request, or listed for a paged call).
 //
 // There is one walk (walk_groups) with two direction policies (ReverseWalk, ForwardWalk).  It is level-
 // synchronous and bit-parallel over groups of 64 requests: a dense u64 visited mask per node (bit =
@@ -39,11 +42,12 @@
 // unpaged answer) run the same steps with three differences.  A walk bit lists no id below its request's
 // cursor (GReq::from).  Every candidate of a confirmation becomes a key request << 32 | id at or above the
 // cursor -- the subject lookup's confirm requests index the ascending domain instead -- and no check is
-// built up front: the sorted unique keys are checked in ascending rounds (page_rounds), at most 64 of a
-// request first, then at most as many again as it has checked, until limit + 1 of its members (walk keys
-// and confirmed candidates) lie at or below the largest id it has checked, or its candidates run out.
-// A walk key above that id stays unplaced: an unchecked candidate may lie below it.  Last, one kernel cuts
-// every request's page out of the sorted unique keys and only the pages go into the pinned block.
+// built up front: the sorted unique keys are checked in ascending rounds (paged_tail, page_rounds: each round
+// one confirm()), at most 64 of a request first, then at most as many again as it has checked, until
+// limit + 1 of its members (walk keys and confirmed candidates) lie at or below the largest id it has
+// checked, or its candidates run out.  A walk key above that id stays unplaced: an unchecked candidate may
+// lie below it.  Last, one kernel cuts every request's page out of the sorted unique keys and only the pages
+// go into the pinned block.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -133,25 +137,26 @@ struct Walk {
   bool paged;         // a paged call: a bit lists only the ids at or above its request's cursor
 };
 
-// The candidate tables of a call: the distinct (ns, rel) of its reverse / confirm-nodes requests and
-// the distinct namespaces of its confirm-all requests, each with the requests that share it.
+// A group table: distinct ascending keys, each with a flag and the requests that share it.
+template <class K>
+struct GroupTab {
+  const K* keys;         // [n] ascending
+  const uint32_t* flag;  // [n]
+  const uint32_t* off;   // [n + 1] into req
+  const uint32_t* req;
+  uint32_t n;
+  __device__ uint32_t count(uint32_t k) const { return off[k + 1] - off[k]; }
+  __device__ const uint32_t* reqs(uint32_t k) const { return req + off[k]; }
+};
+// The candidate tables of a call.
 struct CandTab {
-  const u64* keys;        // [K] ascending (ns << 32 | rel)
-  const uint32_t* kall;   // [K] 1: every node of the key is a candidate (confirm-nodes), 0: impure nodes only
-  const uint32_t* koff;   // [K + 1] into kreq
-  const uint32_t* kreq;
-  uint32_t K;
-  const uint32_t* nsv;    // [M] ascending namespaces
-  const uint32_t* nsoff;  // [M + 1] into nsreq
-  const uint32_t* nsreq;
-  uint32_t M;
-  // the distinct (ns, rel) of the formula requests' relations and leaves, as keys / kall / koff / kreq: a
-  // node of one gives every request of the key a candidate KEY
-  const u64* fkeys;
-  const uint32_t* fall;
-  const uint32_t* foff;
-  const uint32_t* freq;
-  uint32_t FK;
+  // the (ns << 32 | rel) of the reverse / confirm-nodes requests; flag 1: every node of the key is a candidate
+  // (confirm-nodes), 0: impure nodes only
+  GroupTab<u64> rel;
+  GroupTab<uint32_t> ns;  // the namespaces of the confirm-all requests (no flag)
+  // the (ns << 32 | rel) of the formula requests' relations and leaves: a node of one gives every request of
+  // the key a candidate KEY; flag 1: a request's own relation (every live node), 0: a leaf (impure nodes)
+  GroupTab<u64> frel;
 };
 
 // Appends val where pred; one atomic per wave; entries past cap are dropped and flagged.
@@ -502,6 +507,22 @@ __global__ void k_lk_lists_reset(LkCtl* ctl) {
   ctl->tcount = 0;
 }
 
+// ------------------------------------------------------------------ check rows
+// SUBJ: a subject lookup (its requests list subject ids), else an object lookup (object ids).
+template <bool SUBJ>
+using ReqOf = typename std::conditional<SUBJ, kg_lookup_subj, kg_lookup>::type;
+
+// The check of request x on a candidate id: ns:id#rel@subject of an object lookup's request, ns:obj#rel@id
+// of a subject lookup's.
+template <bool SUBJ>
+__device__ __forceinline__ kg_query lk_row(const ReqOf<SUBJ>& x, uint32_t id) {
+  kg_query y;
+  if constexpr (SUBJ) y.t = kg_tuple{x.ns, x.obj, x.rel, KG_SUBJECT_ID, id, 0};
+  else y.t = kg_tuple{x.ns, id, x.rel, x.sns, x.sobj, x.srel};
+  y.max_depth = x.max_depth;
+  return y;
+}
+
 // ------------------------------------------------------------------ candidates of a subject lookup
 // The domain of the confirmation: the subject ids that occur in a tuple.  The holder bitmap has exactly
 // these ids; without it the untagged entries of the check rows are listed (sorted and deduplicated next).
@@ -539,11 +560,7 @@ __global__ __launch_bounds__(256) void k_ls_cands(const uint32_t* __restrict__ d
     const u64 p = at + i, d = p / C;
     if (d >= n_dom) continue;
     const uint32_t r = conf[p % C];
-    const kg_lookup_subj x = q[r];
-    kg_query y;
-    y.t = kg_tuple{x.ns, x.obj, x.rel, KG_SUBJECT_ID, dom[d], 0};
-    y.max_depth = x.max_depth;
-    cq[i] = y;
+    cq[i] = lk_row<true>(q[r], dom[d]);
     creq[i] = r;
   }
 }
@@ -558,25 +575,24 @@ __device__ __forceinline__ void lk_emit_cands(uint32_t c, const uint32_t* reqs, 
     const u64 pos = base + t;
     if (pos >= ccap) break;
     const uint32_t r = reqs[t];
-    const kg_lookup x = q[r];
-    kg_query y;
-    y.t = kg_tuple{x.ns, obj, x.rel, x.sns, x.sobj, x.srel};
-    y.max_depth = x.max_depth;
-    cq[pos] = y;
+    cq[pos] = lk_row<false>(q[r], obj);
     creq[pos] = r;
   }
 }
 
-// A paged call's candidates of object obj: a candidate key (request << 32 | obj) for every request of
-// reqs[0, c) whose cursor obj has reached.  Called by every lane of a wave.
+// Object obj as a candidate key (request << 32 | obj) of every request of reqs[0, c) -- pg (a paged call's
+// pages): of those whose cursor obj has reached.  Called by every lane of a wave.
 __device__ __forceinline__ void lk_emit_keys(uint32_t c, const uint32_t* reqs, uint32_t obj,
                                              const PgReq* __restrict__ pg, u64* kkeys, u64 kcap, LkCtl* ctl) {
-  uint32_t k = 0;
-  for (uint32_t t = 0; t < c; t++) k += obj >= pg[reqs[t]].from ? 1u : 0u;
+  uint32_t k = c;
+  if (pg) {  // the same for every lane
+    k = 0;
+    for (uint32_t t = 0; t < c; t++) k += obj >= pg[reqs[t]].from ? 1u : 0u;
+  }
   u64 at = wave_reserve64(&ctl->kcount, k);
   for (uint32_t t = 0; t < c; t++) {
     const uint32_t r = reqs[t];
-    if (obj < pg[r].from) continue;
+    if (pg && obj < pg[r].from) continue;
     if (at < kcap) kkeys[at] = ((u64)r << 32) | obj;
     at++;
   }
@@ -598,51 +614,41 @@ __global__ __launch_bounds__(256) void k_lk_scan(DevSnap s, CandTab T, const kg_
     if (v < s.n_nodes) {
       const uint32_t ns = s.nd_ns[v], rel = s.nd_rel[v];
       obj = s.nd_obj[v];
-      if (T.K) {
-        k = lk_find(T.keys, T.K, ((u64)ns << 32) | rel);
-        if (k != NONE && (T.kall[k] || (s.nflags && (s.nflags[v] & NF_IMPURE)))) c = T.koff[k + 1] - T.koff[k];
+      if (T.rel.n) {
+        k = lk_find(T.rel.keys, T.rel.n, ((u64)ns << 32) | rel);
+        if (k != NONE && (T.rel.flag[k] || (s.nflags && (s.nflags[v] & NF_IMPURE)))) c = T.rel.count(k);
       }
       // the domain: objects that occur in a tuple -- not the node a refresh left behind without one
-      if (T.M && (!s.nlive || s.nlive[v])) slot = lk_find(T.nsv, T.M, ns);
+      if (T.ns.n && (!s.nlive || s.nlive[v])) slot = lk_find(T.ns.keys, T.ns.n, ns);
     }
-    if constexpr (PAGED) lk_emit_keys(c, c ? T.kreq + T.koff[k] : nullptr, obj, pg, kkeys, kcap, ctl);
-    else lk_emit_cands(c, c ? T.kreq + T.koff[k] : nullptr, obj, q, cq, creq, ccap, ctl);
+    if constexpr (PAGED) lk_emit_keys(c, c ? T.rel.reqs(k) : nullptr, obj, pg, kkeys, kcap, ctl);
+    else lk_emit_cands(c, c ? T.rel.reqs(k) : nullptr, obj, q, cq, creq, ccap, ctl);
     lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
-    if (!T.FK) continue;  // the same for every lane
+    if (!T.frel.n) continue;  // the same for every lane
     // formula requests: the node's object as a candidate key of every request of its (ns, rel)
     uint32_t fc = 0, fk = 0;
     if (v < s.n_nodes) {
       // a node of the requests' own relation counts while it is live; a leaf's node when it is impure --
       // then it has check rows, so its object occurs (nlive is about raw rows: a union node has none)
-      fk = lk_find(T.fkeys, T.FK, ((u64)s.nd_ns[v] << 32) | s.nd_rel[v]);
-      if (fk != NONE && (T.fall[fk] ? (!s.nlive || s.nlive[v]) : (s.nflags && (s.nflags[v] & NF_IMPURE))))
-        fc = T.foff[fk + 1] - T.foff[fk];
+      fk = lk_find(T.frel.keys, T.frel.n, ((u64)s.nd_ns[v] << 32) | s.nd_rel[v]);
+      if (fk != NONE && (T.frel.flag[fk] ? (!s.nlive || s.nlive[v]) : (s.nflags && (s.nflags[v] & NF_IMPURE))))
+        fc = T.frel.count(fk);
     }
-    if constexpr (PAGED) {
-      lk_emit_keys(fc, fc ? T.freq + T.foff[fk] : nullptr, obj, pg, kkeys, kcap, ctl);
-    } else {
-      const u64 at = wave_reserve64(&ctl->kcount, fc);
-      for (uint32_t t = 0; t < fc; t++)
-        if (at + t < kcap) kkeys[at + t] = ((u64)T.freq[T.foff[fk] + t] << 32) | obj;
-    }
+    lk_emit_keys(fc, fc ? T.frel.reqs(fk) : nullptr, obj, PAGED ? pg : nullptr, kkeys, kcap, ctl);
   }
 }
 
-// The unique candidate keys (request << 32 | id) of the formula requests become the checks
-// cq[at, at + m): ns:id#rel@subject of an object lookup's request, ns:obj#rel@id of a subject lookup's.
-template <bool SUBJ, class Req>
-__global__ __launch_bounds__(256) void k_lk_key_cands(const u64* __restrict__ uk, u64 m, const Req* __restrict__ q,
-                                                      uint32_t n_reqs, kg_query* cq, uint32_t* creq) {
+// Keys become the checks cq[0, m).  ID_HIGH false: candidate keys request << 32 | id (the formula requests'
+// unique keys); true: id << 32 | request (a paged subject round sorted by subject id, k_pg_rows).
+template <bool SUBJ, bool ID_HIGH>
+__global__ __launch_bounds__(256) void k_lk_key_rows(const u64* __restrict__ keys, u64 m,
+                                                     const ReqOf<SUBJ>* __restrict__ q, uint32_t n_reqs, kg_query* cq,
+                                                     uint32_t* creq) {
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
-    const u64 key = uk[i];
-    const uint32_t r = min((uint32_t)(key >> 32), n_reqs - 1), id = (uint32_t)key;
-    const Req x = q[r];
-    kg_query y;
-    if constexpr (SUBJ) y.t = kg_tuple{x.ns, x.obj, x.rel, KG_SUBJECT_ID, id, 0};
-    else y.t = kg_tuple{x.ns, id, x.rel, x.sns, x.sobj, x.srel};
-    y.max_depth = x.max_depth;
-    cq[i] = y;
+    const uint32_t hi = (uint32_t)(keys[i] >> 32), lo = (uint32_t)keys[i];
+    const uint32_t r = min(ID_HIGH ? lo : hi, n_reqs - 1);
+    cq[i] = lk_row<SUBJ>(q[r], ID_HIGH ? hi : lo);
     creq[i] = r;
   }
 }
@@ -663,42 +669,68 @@ __global__ __launch_bounds__(256) void k_lk_domain(CandTab T, const u64* __restr
       if (i == 0 || dk[i - 1] != key) {
         slot = (uint32_t)(key >> 32);
         obj = (uint32_t)key;
-        if (slot < T.M) c = T.nsoff[slot + 1] - T.nsoff[slot];
+        if (slot < T.ns.n) c = T.ns.count(slot);
       }
     }
-    if constexpr (PAGED) lk_emit_keys(c, c ? T.nsreq + T.nsoff[slot] : nullptr, obj, pg, kkeys, kcap, ctl);
-    else lk_emit_cands(c, c ? T.nsreq + T.nsoff[slot] : nullptr, obj, q, cq, creq, ccap, ctl);
+    if constexpr (PAGED) lk_emit_keys(c, c ? T.ns.reqs(slot) : nullptr, obj, pg, kkeys, kcap, ctl);
+    else lk_emit_cands(c, c ? T.ns.reqs(slot) : nullptr, obj, q, cq, creq, ccap, ctl);
   }
 }
 
-// The candidates' answers: members join the output keys; errors are counted per request, with the code
-// of the lowest object id (errmin: object << 32 | code, atomicMin).  SUBJ: the candidates of a subject
-// lookup -- the listed id is the query's subject id.
-template <bool SUBJ>
+// Where a collect sends the first pass's members and errors.  Called by every lane of a wave (mem: the
+// lane's candidate id of request r is a member; bad: it erred with `code`).
+// An unpaged call: errors are counted per request, with the code of the lowest id (errmin: id << 32 | code).
+struct ErrCount {
+  u64* n_errors;
+  u64* errmin;
+  __device__ void operator()(bool, bool bad, uint32_t r, uint32_t id, uint32_t code, LkCtl*) const {
+    if (!bad) return;
+    atomicAdd(&n_errors[r], 1ull);
+    atomicMin(&errmin[r], ((u64)id << 32) | code);
+  }
+};
+// A paged call: a member joins its request's count; an erring id goes with its code to the error list
+// (ekeys: request << 32 | id) -- which of them a page covers is known at the end (k_pg_errs).
+struct ErrList {
+  PgReq* pg;
+  u64* ekeys;
+  uint32_t* ecodes;
+  u64 ecap;
+  __device__ void operator()(bool mem, bool bad, uint32_t r, uint32_t id, uint32_t code, LkCtl* ctl) const {
+    if (mem) atomicAdd(&pg[r].nmem, 1ull);
+    const u64 ep = wave_reserve64(&ctl->ecount, bad ? 1u : 0u);
+    if (bad && ep < ecap) {
+      ekeys[ep] = ((u64)r << 32) | id;
+      ecodes[ep] = code;
+    }
+  }
+};
+
+// The candidates' answers: members join the output keys (request << 32 | id) and the `confirmed` count,
+// errors go to the sink.  SUBJ: the listed id is the query's subject id.  first == 0: a rerun after the
+// output list grew -- only the output keys are written again.
+template <bool SUBJ, class Sink>
 __global__ __launch_bounds__(256) void k_lk_collect(const kg_query* __restrict__ cq, const uint32_t* __restrict__ creq,
                                                     const uint8_t* __restrict__ out, const uint32_t* __restrict__ err,
-                                                    u64 n, u64* okeys, u64 ocap, int count_errs, u64* n_errors,
-                                                    u64* errmin, LkCtl* ctl) {
+                                                    u64 n, u64* okeys, u64 ocap, int first, Sink sink, LkCtl* ctl) {
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n; base += stride) {
     const u64 i = base + lane_id();
-    bool mem = false;
-    u64 key = 0;
+    bool mem = false, bad = false;
+    uint32_t r = 0, id = 0;
     if (i < n) {
       const uint8_t o = out[i];
-      const uint32_t r = creq[i], obj = SUBJ ? cq[i].t.sobj : cq[i].t.obj;
+      r = creq[i];
+      id = SUBJ ? cq[i].t.sobj : cq[i].t.obj;
       mem = o == KG_IS_MEMBER;
-      key = ((u64)r << 32) | obj;
-      if (o == KG_ERROR && count_errs) {
-        atomicAdd(&n_errors[r], 1ull);
-        atomicMin(&errmin[r], ((u64)obj << 32) | err[i]);
-      }
+      bad = o == KG_ERROR;
     }
-    if (count_errs) {
+    if (first) {
       const uint64_t mm = __ballot(mem);
       if (mm && lane_id() == 0) atomicAdd(&ctl->confirmed, (u64)__popcll(mm));
+      sink(mem, bad, r, id, bad ? err[i] : 0u, ctl);
     }
-    lk_append64(mem, key, okeys, &ctl->ocount, ocap);
+    lk_append64(mem, ((u64)r << 32) | id, okeys, &ctl->ocount, ocap);
   }
 }
 
@@ -719,6 +751,13 @@ __global__ __launch_bounds__(256) void k_lk_finish(const u64* __restrict__ uk, u
 // ------------------------------------------------------------------ paged calls: rounds and the page
 constexpr u64 PG_FIRST = 64;            // a request's first round checks at most this many candidates
 constexpr u64 PG_ROUND_MAX = 1ull << 22;  // and no round more than this many of one request
+// The rows one check_batch_device call of a confirmation takes (confirm()).
+// unpaged object candidates: the scan has built every row before the first check; the size was never measured
+constexpr u64 CHUNK_OBJECTS = 1ull << 28;
+// unpaged subject candidates: rows are built a chunk at a time, so this bounds the check buffers (4 Mi rows)
+constexpr u64 CHUNK_SUBJECTS = 1ull << 22;
+// a paged round: its rows are all built first, like the object candidates'; smaller than theirs, never measured
+constexpr u64 CHUNK_ROUND = 1ull << 26;
 
 // the id of entry i of request x's run of candidates
 __device__ __forceinline__ uint32_t pg_cand(const PgReq& x, u64 i, const u64* __restrict__ uk,
@@ -778,95 +817,27 @@ __global__ __launch_bounds__(256) void k_pg_plan(uint32_t n, PgTake take, u64* _
   if (threadIdx.x == 0) ctl->ptotal = pref[n];
 }
 
-// The round's slices as kg_query rows: ns:id#rel@subject of an object lookup's request, ns:obj#rel@id of
-// a subject lookup's.
-template <bool SUBJ, class Req>
+// The round's slices as kg_query rows, request-major -- or, keys != nullptr, as keys id << 32 | request: a
+// subject lookup's round is sorted by them before its rows are built (k_lk_key_rows), so that neighbouring
+// checks share their subject id, as the unpaged confirmation's pairs do -- the check tiers answer such a
+// batch several times faster than one whose neighbours share the object.
+constexpr u64 PG_SORT_MIN = 4096;  // smaller rounds are bound by their launches, not by the checks
+template <bool SUBJ>
 __global__ __launch_bounds__(256) void k_pg_rows(const PgReq* __restrict__ pg, uint32_t n, const u64* __restrict__ pref,
                                                  const u64* __restrict__ uk, const uint32_t* __restrict__ dom,
-                                                 const Req* __restrict__ q, kg_query* cq, uint32_t* creq) {
+                                                 const ReqOf<SUBJ>* __restrict__ q, kg_query* cq, uint32_t* creq,
+                                                 u64* __restrict__ keys) {
   const u64 total = pref[n], stride = (u64)gridDim.x * 256;
   for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
     const uint32_t r = csr_owner((const uint64_t*)pref, n, e);
     const PgReq& x = pg[r];
-    const u64 at = x.base + (e - pref[r]);
-    if (at >= x.hi) continue;  // never: the slice lies in the run
-    const uint32_t id = pg_cand(x, at, uk, dom);
-    const Req y = q[r];
-    kg_query z;
-    if constexpr (SUBJ) z.t = kg_tuple{y.ns, y.obj, y.rel, KG_SUBJECT_ID, id, 0};
-    else z.t = kg_tuple{y.ns, id, y.rel, y.sns, y.sobj, y.srel};
-    z.max_depth = y.max_depth;
-    cq[e] = z;
+    const uint32_t id = pg_cand(x, min(x.base + (e - pref[r]), x.hi - 1), uk, dom);  // the slice lies in the run
+    if (keys) {
+      keys[e] = ((u64)id << 32) | r;
+      continue;
+    }
+    cq[e] = lk_row<SUBJ>(q[r], id);
     creq[e] = r;
-  }
-}
-
-// A subject lookup's round as keys id << 32 | request: once sorted, neighbouring checks share their subject
-// id, as the unpaged confirmation's pairs do -- the check tiers answer such a batch several times faster
-// than one whose neighbours share the object.
-constexpr u64 PG_SORT_MIN = 4096;  // smaller rounds are bound by their launches, not by the checks
-__global__ __launch_bounds__(256) void k_pg_round_keys(const PgReq* __restrict__ pg, uint32_t n,
-                                                       const u64* __restrict__ pref, const u64* __restrict__ uk,
-                                                       const uint32_t* __restrict__ dom, u64* __restrict__ keys) {
-  const u64 total = pref[n], stride = (u64)gridDim.x * 256;
-  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-    const uint32_t r = csr_owner((const uint64_t*)pref, n, e);
-    const PgReq& x = pg[r];
-    const u64 at = min(x.base + (e - pref[r]), x.hi - 1);  // the slice lies in the run
-    keys[e] = ((u64)pg_cand(x, at, uk, dom) << 32) | r;
-  }
-}
-__global__ __launch_bounds__(256) void k_pg_key_rows(const u64* __restrict__ keys, u64 total,
-                                                     const kg_lookup_subj* __restrict__ q, uint32_t n, kg_query* cq,
-                                                     uint32_t* creq) {
-  const u64 stride = (u64)gridDim.x * 256;
-  for (u64 e = (u64)blockIdx.x * 256 + threadIdx.x; e < total; e += stride) {
-    const u64 key = keys[e];
-    const uint32_t r = min((uint32_t)key, n - 1), id = (uint32_t)(key >> 32);
-    const kg_lookup_subj y = q[r];
-    kg_query z;
-    z.t = kg_tuple{y.ns, y.obj, y.rel, KG_SUBJECT_ID, id, 0};
-    z.max_depth = y.max_depth;
-    cq[e] = z;
-    creq[e] = r;
-  }
-}
-
-// The round's answers: members join the output keys and their request's count; an erring id goes with
-// its code to the error list (ekeys: request << 32 | id).  first == 0: a rerun after the output list
-// grew -- only the output keys are written again.
-template <bool SUBJ>
-__global__ __launch_bounds__(256) void k_pg_collect(const kg_query* __restrict__ cq, const uint32_t* __restrict__ creq,
-                                                    const uint8_t* __restrict__ out, const uint32_t* __restrict__ err,
-                                                    u64 n, u64* okeys, u64 ocap, int first, PgReq* pg, u64* ekeys,
-                                                    uint32_t* ecodes, u64 ecap, LkCtl* ctl) {
-  const u64 stride = (u64)gridDim.x * 256;
-  for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n; base += stride) {
-    const u64 i = base + lane_id();
-    bool mem = false, bad = false;
-    u64 key = 0;
-    uint32_t code = 0;
-    if (i < n) {
-      const uint8_t o = out[i];
-      const uint32_t r = creq[i], id = SUBJ ? cq[i].t.sobj : cq[i].t.obj;
-      mem = o == KG_IS_MEMBER;
-      key = ((u64)r << 32) | id;
-      if (first) {
-        if (mem) atomicAdd(&pg[r].nmem, 1ull);
-        bad = o == KG_ERROR;
-        code = err[i];
-      }
-    }
-    if (first) {
-      const uint64_t mm = __ballot(mem);
-      if (mm && lane_id() == 0) atomicAdd(&ctl->confirmed, (u64)__popcll(mm));
-    }
-    lk_append64(mem, key, okeys, &ctl->ocount, ocap);
-    const u64 ep = wave_reserve64(&ctl->ecount, bad ? 1u : 0u);
-    if (bad && ep < ecap) {
-      ekeys[ep] = key;
-      ecodes[ep] = code;
-    }
   }
 }
 
@@ -1066,6 +1037,9 @@ struct Call {
     return 0;
   }
 
+  // a grid for n items, one per thread
+  dim3 grid(u64 n) const { return dim3((uint32_t)std::min<u64>(grid_wide, n / 256 + 1)); }
+
   int read_ctl(LkCtl* h) {
     void* hb = w->host_buf(65536);
     if (!hb) return set_error(-1, "pinned host buffer");
@@ -1080,8 +1054,9 @@ struct Call {
   // the m ids of B.d_objs with B.d_off / n_errors / d_ecode (and d_next: a paged call's next[n]) copied
   // into one pinned block; the call's counters
   int deliver(kg_lookup_buf* out, u64 m, uint32_t** next);
-  // a paged call: the requests' pages on the device (implicit[i]: request i's candidates are the domain)
-  int page_upload(const std::vector<uint8_t>& implicit);
+  // a paged call: the requests' cursors on the walk's bits, their pages on the device (implicit[i]: request
+  // i's candidates are the domain)
+  int page_upload(std::vector<GReq>& greq, const std::vector<uint8_t>& implicit);
   // the end of a paged call: every request's page cut out of the sorted unique keys
   int finish_page(kg_lookup_pages* out, const u64* uk, const uint32_t* dom);
 };
@@ -1122,9 +1097,8 @@ int Call::finish(kg_lookup_buf* out) {
   HIPC(B.d_off.reserve(n + 1));
   HIPC(B.d_objs.reserve((size_t)std::max<u64>(m, 1)));
   HIPC(B.d_ecode.reserve(n));
-  hipLaunchKernelGGL(k_lk_finish, dim3((uint32_t)std::min<u64>(grid_wide, std::max<u64>(m, n + 1) / 256 + 1)), dim3(256),
-                     0, st, uk, m, (uint32_t)n, B.d_off.get(), B.d_objs.get(), (const u64*)B.errmin.get(),
-                     B.d_ecode.get());
+  hipLaunchKernelGGL(k_lk_finish, grid(std::max<u64>(m, n + 1)), dim3(256), 0, st, uk, m, (uint32_t)n, B.d_off.get(),
+                     B.d_objs.get(), (const u64*)B.errmin.get(), B.d_ecode.get());
   HIPC(hipGetLastError());
   return deliver(out, m, nullptr);
 }
@@ -1175,15 +1149,22 @@ int Call::deliver(kg_lookup_buf* out, u64 m, uint32_t** next) {
   return 0;
 }
 
-// The candidates' answers join the output keys (k_lk_collect); errors are counted on the first pass only.
-template <bool SUBJ>
-int collect(Call& c, u64 n_cand) {
+// f(std::true_type) or f(std::false_type): a kernel's template flag from a runtime one.
+template <class F>
+void with_flag(bool flag, F f) {
+  if (flag) f(std::true_type{});
+  else f(std::false_type{});
+}
+
+// The answers of the candidates B.cq[0, n_cand) join the output keys (k_lk_collect).  The output list grows
+// once at most: the second pass writes the keys alone, members and errors are counted on the first.
+template <bool SUBJ, class Sink>
+int collect(Call& c, u64 n_cand, const Sink& sink) {
   LookupBufs& B = c.B;
   for (int pass = 0;; pass++) {
-    hipLaunchKernelGGL(k_lk_collect<SUBJ>, dim3((uint32_t)std::min<u64>(c.grid_wide, n_cand / 256 + 1)), dim3(256), 0,
-                       c.st, (const kg_query*)B.cq.get(), (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(),
-                       (const uint32_t*)B.cerr.get(), n_cand, B.okeys.get(), c.O.cap, pass == 0 ? 1 : 0,
-                       B.n_errors.get(), B.errmin.get(), B.ctl.get());
+    hipLaunchKernelGGL((k_lk_collect<SUBJ, Sink>), c.grid(n_cand), dim3(256), 0, c.st, (const kg_query*)B.cq.get(),
+                       (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(), (const uint32_t*)B.cerr.get(), n_cand,
+                       B.okeys.get(), c.O.cap, pass == 0 ? 1 : 0, sink, B.ctl.get());
     HIPC(hipGetLastError());
     LkCtl h;
     if (int rc = c.read_ctl(&h)) return rc;
@@ -1194,13 +1175,51 @@ int collect(Call& c, u64 n_cand) {
       continue;
     }
     c.n_conf = h.confirmed;
+    c.n_ekeys = h.ecount;  // a paged call's error list (ErrList); 0 in an unpaged call
     return 0;
   }
 }
 
-// The call's candidate keys sorted, one of each: uk[0, *m).
+// One confirmation: `total` candidates as kg_query rows through check_batch_device, `chunk` rows a call, and
+// their answers collected.  whole: rows(0, total) builds every row (B.cq / B.creq [0, total)) before the
+// first check and one collect follows the last; else rows(at, m) builds the rows of chunk [at, at + m) at
+// the head of the buffers and each chunk is checked and collected before the next is built.
+template <bool SUBJ, class Rows, class Sink>
+int confirm(Call& c, u64 total, u64 chunk, bool whole, const Rows& rows, const Sink& sink) {
+  if (!total) return 0;
+  LookupBufs& B = c.B;
+  const u64 span = whole ? total : std::min(chunk, total);  // rows built, and collected, at a time
+  HIPC(B.cq.reserve((size_t)span));  // keeps what it holds when that is large enough (the scan's rows)
+  HIPC(B.creq.reserve((size_t)span));
+  HIPC(B.cout.reserve((size_t)span));
+  HIPC(B.cerr.reserve((size_t)span));
+  for (u64 at = 0; at < total; at += span) {
+    const u64 m = std::min(span, total - at);
+    if (int rc = rows(at, m)) return rc;
+    HIPC(hipGetLastError());
+    for (u64 k = 0; k < m; k += chunk) {
+      const size_t kn = (size_t)std::min(chunk, m - k);
+      if (int rc = check_batch_device(c.s, c.w, B.cq.get() + k, kn, c.gmax, B.cout.get() + k, B.cerr.get() + k, nullptr))
+        return rc;
+    }
+    if (int rc = collect<SUBJ>(c, m, sink)) return rc;
+  }
+  c.n_cand += total;
+  return 0;
+}
+
+// The keys[0, m) as the rows cq[0, m) (k_lk_key_rows).
+template <bool SUBJ, bool ID_HIGH>
+void launch_key_rows(Call& c, const u64* keys, u64 m, kg_query* cq, uint32_t* creq) {
+  hipLaunchKernelGGL((k_lk_key_rows<SUBJ, ID_HIGH>), c.grid(m), dim3(256), 0, c.st, keys, m,
+                     (const ReqOf<SUBJ>*)c.B.d_req.get(), (uint32_t)c.n, cq, creq);
+}
+
+// The call's candidate keys sorted, one of each: uk[0, *m) (a call without one: nullptr, 0).
 int unique_cand_keys(Call& c, const u64** uk, u64* m) {
-  return sort_keys(c, c.B.kkeys, c.B.kkeys2, (size_t)c.K.have, key_bits(c.n), uk, m);
+  *uk = nullptr;
+  *m = 0;
+  return !c.K.have ? 0 : sort_keys(c, c.B.kkeys, c.B.kkeys2, (size_t)c.K.have, key_bits(c.n), uk, m);
 }
 
 // buf holds at least `need` entries and still its first `keep`.
@@ -1216,7 +1235,8 @@ int keep_grow(Call& c, DevBuf<T>& buf, size_t keep, size_t need) {
 }
 
 // ------------------------------------------------------------------ host: a paged call
-int Call::page_upload(const std::vector<uint8_t>& implicit) {
+int Call::page_upload(std::vector<GReq>& greq, const std::vector<uint8_t>& implicit) {
+  for (GReq& g : greq) g.from = pg[g.req].from;
   std::vector<PgReq> h(n);
   for (size_t i = 0; i < n; i++) h[i] = PgReq{0, 0, 0, 0, 0, pg[i].from, pg[i].limit, implicit.empty() ? 0u : implicit[i], 0};
   HIPC(B.pst.reserve(n));
@@ -1225,34 +1245,10 @@ int Call::page_upload(const std::vector<uint8_t>& implicit) {
   return 0;
 }
 
-// A round's answers collected (k_pg_collect); the output list grows like collect()'s.
-template <bool SUBJ>
-int collect_page(Call& c, u64 total) {
-  LookupBufs& B = c.B;
-  for (int pass = 0;; pass++) {
-    hipLaunchKernelGGL(k_pg_collect<SUBJ>, dim3((uint32_t)std::min<u64>(c.grid_wide, total / 256 + 1)), dim3(256), 0, c.st,
-                       (const kg_query*)B.cq.get(), (const uint32_t*)B.creq.get(), (const uint8_t*)B.cout.get(),
-                       (const uint32_t*)B.cerr.get(), total, B.okeys.get(), c.O.cap, pass == 0 ? 1 : 0, B.pst.get(),
-                       B.ekeys.get(), B.ecodes.get(), (u64)std::min(B.ekeys.cap(), B.ecodes.cap()), B.ctl.get());
-    HIPC(hipGetLastError());
-    LkCtl h;
-    if (int rc = c.read_ctl(&h)) return rc;
-    bool again = false;
-    if (int rc = c.settle(h, &again)) return rc;
-    if (again) {
-      if (pass) return set_error(KG_ERR_RESOURCE_CODE, "lookup: output list overflowed twice");
-      continue;
-    }
-    c.n_conf = h.confirmed;
-    c.n_ekeys = h.ecount;
-    return 0;
-  }
-}
-
 // The confirmation of a paged call in ascending rounds.  uk[0, m): the call's sorted unique candidate
 // keys; dom[0, n_dom): the domain of the implicit requests (any_implicit: there is one).  A call without
 // candidates takes no round.
-template <bool SUBJ, class Req>
+template <bool SUBJ>
 int page_rounds(Call& c, const u64* uk, u64 m, const uint32_t* dom, u64 n_dom, bool any_implicit) {
   LookupBufs& B = c.B;
   const uint32_t n = (uint32_t)c.n, blocks = (n + 255) / 256;
@@ -1281,39 +1277,25 @@ int page_rounds(Call& c, const u64* uk, u64 m, const uint32_t* dom, u64 n_dom, b
     const u64 total = h.ptotal;
     if (!total) return 0;
     c.n_rounds++;
-    HIPC(B.cq.reserve((size_t)total));
-    HIPC(B.creq.reserve((size_t)total));
-    HIPC(B.cout.reserve((size_t)total));
-    HIPC(B.cerr.reserve((size_t)total));
     if (int rc = keep_grow(c, B.ekeys, (size_t)c.n_ekeys, (size_t)(c.n_ekeys + total))) return rc;
     if (int rc = keep_grow(c, B.ecodes, (size_t)c.n_ekeys, (size_t)(c.n_ekeys + total))) return rc;
-    const dim3 rgrid((uint32_t)std::min<u64>(c.grid_wide, total / 256 + 1));
-    bool by_subject = false;
-    if constexpr (SUBJ) {
-      if (total >= PG_SORT_MIN) {  // the round's checks ordered by subject id
-        by_subject = true;
-        HIPC(B.rkeys.reserve((size_t)total));
-        hipLaunchKernelGGL(k_pg_round_keys, rgrid, dim3(256), 0, c.st, (const PgReq*)B.pst.get(), n,
-                           (const u64*)B.ppref.get(), uk, dom, B.rkeys.get());
+    // the round's rows, request-major -- a subject round of PG_SORT_MIN checks or more ordered by subject id
+    auto rows = [&](u64, u64) -> int {
+      const bool by_subject = SUBJ && total >= PG_SORT_MIN;
+      if (by_subject) HIPC(B.rkeys.reserve((size_t)total));
+      hipLaunchKernelGGL(k_pg_rows<SUBJ>, c.grid(total), dim3(256), 0, c.st, (const PgReq*)B.pst.get(), n,
+                         (const u64*)B.ppref.get(), uk, dom, (const ReqOf<SUBJ>*)B.d_req.get(), B.cq.get(), B.creq.get(),
+                         by_subject ? B.rkeys.get() : nullptr);
+      if (by_subject) {  // the round's keys sorted, then its rows
         HIPC(hipGetLastError());
         const u64* sk = nullptr;
         if (int rc = sort_keys(c, B.rkeys, B.rkeys2, (size_t)total, 64, &sk, (u64*)nullptr)) return rc;
-        hipLaunchKernelGGL(k_pg_key_rows, rgrid, dim3(256), 0, c.st, sk, total, (const kg_lookup_subj*)B.d_req.get(), n,
-                           B.cq.get(), B.creq.get());
+        launch_key_rows<true, true>(c, sk, total, B.cq.get(), B.creq.get());
       }
-    }
-    if (!by_subject)
-      hipLaunchKernelGGL((k_pg_rows<SUBJ, Req>), rgrid, dim3(256), 0, c.st, (const PgReq*)B.pst.get(), n,
-                         (const u64*)B.ppref.get(), uk, dom, (const Req*)B.d_req.get(), B.cq.get(), B.creq.get());
-    HIPC(hipGetLastError());
-    constexpr u64 CHUNK = 1ull << 26;
-    for (u64 at = 0; at < total; at += CHUNK) {
-      const size_t k = (size_t)std::min(CHUNK, total - at);
-      if (int rc = check_batch_device(c.s, c.w, B.cq.get() + at, k, c.gmax, B.cout.get() + at, B.cerr.get() + at, nullptr))
-        return rc;
-    }
-    if (int rc = collect_page<SUBJ>(c, total)) return rc;
-    c.n_cand += total;
+      return 0;
+    };
+    const ErrList sink{B.pst.get(), B.ekeys.get(), B.ecodes.get(), (u64)std::min(B.ekeys.cap(), B.ecodes.cap())};
+    if (int rc = confirm<SUBJ>(c, total, CHUNK_ROUND, true, rows, sink)) return rc;
   }
 }
 
@@ -1331,8 +1313,8 @@ int Call::finish_page(kg_lookup_pages* out, const u64* uk, const uint32_t* dom) 
   hipLaunchKernelGGL(k_pg_finish, dim3(blocks), dim3(256), 0, st, (const PgReq*)B.pst.get(), nr, fk, m, uk, dom,
                      B.pkept.get(), B.pklo.get(), B.d_next.get());
   if (n_ekeys)
-    hipLaunchKernelGGL(k_pg_errs, dim3((uint32_t)std::min<u64>(grid_wide, n_ekeys / 256 + 1)), dim3(256), 0, st,
-                       (const u64*)B.ekeys.get(), (const uint32_t*)B.ecodes.get(), n_ekeys, (const PgReq*)B.pst.get(), nr,
+    hipLaunchKernelGGL(k_pg_errs, grid(n_ekeys), dim3(256), 0, st, (const u64*)B.ekeys.get(),
+                       (const uint32_t*)B.ecodes.get(), n_ekeys, (const PgReq*)B.pst.get(), nr,
                        (const uint32_t*)B.d_next.get(), B.n_errors.get(), B.errmin.get());
   hipLaunchKernelGGL(k_pg_offsets, dim3(1), dim3(256), 0, st, nr, PgKept{B.pkept.get()}, B.d_off.get(), B.ctl.get());
   HIPC(hipGetLastError());
@@ -1340,9 +1322,9 @@ int Call::finish_page(kg_lookup_pages* out, const u64* uk, const uint32_t* dom) 
   if (int rc = read_ctl(&h)) return rc;
   const u64 total = std::min(h.ptotal, m);
   HIPC(B.d_objs.reserve((size_t)std::max<u64>(total, 1)));
-  hipLaunchKernelGGL(k_pg_gather, dim3((uint32_t)std::min<u64>(grid_wide, std::max<u64>(total, n) / 256 + 1)), dim3(256), 0,
-                     st, fk, (const u64*)B.pklo.get(), (const uint64_t*)B.d_off.get(), nr, total, B.d_objs.get(),
-                     (const u64*)B.errmin.get(), B.d_ecode.get());
+  hipLaunchKernelGGL(k_pg_gather, grid(std::max<u64>(total, n)), dim3(256), 0, st, fk, (const u64*)B.pklo.get(),
+                     (const uint64_t*)B.d_off.get(), nr, total, B.d_objs.get(), (const u64*)B.errmin.get(),
+                     B.d_ecode.get());
   HIPC(hipGetLastError());
   if (int rc = deliver(&out->list, total, &out->next)) return rc;
   out->rounds = n_rounds;
@@ -1533,329 +1515,335 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
   return 0;
 }
 
+// ------------------------------------------------------------------ host: the ends both lookups share
+// The end of a paged call: every candidate is a key -- one of each, checked in ascending rounds (a subject
+// lookup's confirm requests index the domain dom[0, n_dom) instead) -- and the pages cut out.
+template <bool SUBJ>
+int paged_tail(Call& c, const uint32_t* dom, u64 n_dom, bool any_implicit, kg_lookup_pages* out) {
+  const u64* uk;
+  u64 m;
+  if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
+  if (int rc = page_rounds<SUBJ>(c, uk, m, dom, n_dom, any_implicit)) return rc;
+  return c.finish_page(out, uk, dom);
+}
+
+// ------------------------------------------------------------------ host: the steps of an object lookup
+// The plan: the walk's request bits, and the requests grouped by what makes a node their candidate.
+struct ObjPlan {
+  std::vector<GReq> greq;
+  std::map<u64, std::vector<uint32_t>> by_rel, by_frel;  // ns << 32 | rel -> requests (CandTab::rel, ::frel)
+  std::map<uint32_t, std::vector<uint32_t>> by_ns;       // CandTab::ns
+  bool tables() const { return !by_rel.empty() || !by_ns.empty() || !by_frel.empty(); }
+};
+int plan_objects(Call& c, const kg_lookup* reqs, const LReq* lr, ObjPlan* P) {
+  const Snapshot* s = c.s;
+  for (size_t i = 0; i < c.n; i++) {
+    if (lr[i].mode == LK_ALL) {
+      P->by_ns[reqs[i].ns].push_back((uint32_t)i);
+      continue;
+    }
+    if (lr[i].mode == LK_FORMULA) {
+      if (lr[i].plan >= s->h_fplans.size()) return set_error(-1, "lookup: formula plan out of range");
+      const FPlan& F = s->h_fplans[lr[i].plan];
+      // the walk listens to the walk leaves; the scan takes the relation and every leaf
+      GReq g{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 0, {}};
+      P->by_frel[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
+      for (uint32_t j = 0; j < F.n_leaves && j < (uint32_t)FP_LEAVES; j++) {
+        P->by_frel[((u64)reqs[i].ns << 32) | F.leaf[j]].push_back((uint32_t)i);
+        if ((F.walk_leaves >> j) & 1u) g.listen[g.n_listen++] = F.leaf[j];
+      }
+      if (lr[i].hcount && g.n_listen) P->greq.push_back(g);
+      continue;
+    }
+    if (lr[i].mode == LK_REVERSE && lr[i].hcount)
+      P->greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 1, {reqs[i].rel}});
+    // candidates of a reverse request: impure nodes -- none without node flags
+    if (lr[i].mode == LK_NODES || s->ds.nflags) P->by_rel[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
+  }
+  return 0;
+}
+
+// The table of `by` appended to blob (u32 words, 64-bit keys on 8 bytes, low word first): keys[n] | flag[n] |
+// off[n + 1] | req[..]; returns where it starts.  flag(key, its requests): the key's flag.
+template <class K, class Flag>
+size_t tab_append(std::vector<uint32_t>& blob, const std::map<K, std::vector<uint32_t>>& by, Flag flag) {
+  if (blob.size() & 1) blob.push_back(0);
+  const size_t at = blob.size();
+  for (auto& kv : by) {
+    blob.push_back((uint32_t)kv.first);
+    if (sizeof(K) == 8) blob.push_back((uint32_t)((u64)kv.first >> 32));
+  }
+  for (auto& kv : by) blob.push_back(flag(kv.first, kv.second) ? 1u : 0u);
+  uint32_t n_req = 0;
+  for (auto& kv : by) {
+    blob.push_back(n_req);
+    n_req += (uint32_t)kv.second.size();
+  }
+  blob.push_back(n_req);
+  for (auto& kv : by) blob.insert(blob.end(), kv.second.begin(), kv.second.end());
+  return at;
+}
+// The table of n keys that tab_append put at word `at` of the blob, now at base on the device.
+template <class K>
+GroupTab<K> tab_on(const uint32_t* base, size_t at, size_t n) {
+  const uint32_t* flag = base + at + n * (sizeof(K) / 4);
+  return GroupTab<K>{(const K*)(base + at), flag, flag + n, flag + 2 * n + 1, (uint32_t)n};
+}
+
+// The plan's three tables, uploaded as one blob (B.tab).
+int upload_tables(Call& c, const ObjPlan& P, const kg_lookup* reqs, const LReq* lr, CandTab* T) {
+  typedef const std::vector<uint32_t>& Reqs;
+  std::vector<uint32_t> blob;
+  const size_t rel = tab_append(blob, P.by_rel, [&](u64, Reqs rs) { return lr[rs[0]].mode == LK_NODES; });
+  const size_t ns = tab_append(blob, P.by_ns, [](uint32_t, Reqs) { return false; });
+  // every node of a request's own relation (its rows join the answer), the impure nodes of a leaf
+  const size_t frel = tab_append(blob, P.by_frel, [&](u64 key, Reqs rs) {
+    bool own = false;
+    for (uint32_t r : rs) own |= reqs[r].rel == (uint32_t)key;
+    return own;
+  });
+  blob.push_back(0);
+  HIPC(c.B.tab.reserve(blob.size() + 2));
+  HIPC(hipMemcpyAsync(c.B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, c.st));
+  HIPC(hipStreamSynchronize(c.st));  // blob is pageable
+  const uint32_t* tb = c.B.tab.get();
+  *T = CandTab{tab_on<u64>(tb, rel, P.by_rel.size()), tab_on<uint32_t>(tb, ns, P.by_ns.size()),
+               tab_on<u64>(tb, frel, P.by_frel.size())};
+  return 0;
+}
+
+// One pass over the nodes (k_lk_scan) into lists of ccap checks and dcap domain keys; *h: the counters after.
+int scan_nodes(Call& c, const CandTab& T, u64 ccap, u64 dcap, LkCtl* h) {
+  LookupBufs& B = c.B;
+  const bool paged = c.pg != nullptr;
+  HIPC(B.cq.reserve((size_t)ccap));
+  HIPC(B.creq.reserve((size_t)ccap));
+  if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
+  HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, c.st));  // ccount, dcount
+  if (T.frel.n || paged)  // the candidate keys back at the walk's
+    if (int rc = c.rewind()) return rc;
+  const dim3 grid(std::max(1u, std::min(c.grid_wide, c.s->ds.n_nodes / 256 + 1)));
+  with_flag(paged, [&](auto P) {
+    hipLaunchKernelGGL(k_lk_scan<decltype(P)::value>, grid, dim3(256), 0, c.st, c.s->ds, T, (const kg_lookup*)B.d_req.get(),
+                       B.cq.get(), B.creq.get(), ccap, B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap,
+                       (const PgReq*)B.pst.get(), B.ctl.get());
+  });
+  HIPC(hipGetLastError());
+  return c.read_ctl(h);
+}
+// The nd domain keys sorted, every distinct object a candidate of its namespace's requests (k_lk_domain).
+int scan_domain(Call& c, const CandTab& T, u64 ccap, size_t nd, LkCtl* h) {
+  LookupBufs& B = c.B;
+  const u64* dk = nullptr;
+  if (int rc = sort_keys(c, B.dkeys, B.dkeys2, nd, 64, &dk, (u64*)nullptr)) return rc;
+  with_flag(c.pg != nullptr, [&](auto P) {
+    hipLaunchKernelGGL(k_lk_domain<decltype(P)::value>, c.grid(nd), dim3(256), 0, c.st, T, dk, (u64)nd,
+                       (const kg_lookup*)B.d_req.get(), B.cq.get(), B.creq.get(), ccap, B.kkeys.get(), c.K.cap,
+                       (const PgReq*)B.pst.get(), B.ctl.get());
+  });
+  HIPC(hipGetLastError());
+  return c.read_ctl(h);
+}
+// The candidates: one pass over the nodes, then the sorted domains of the confirm-all namespaces; both again
+// when a list was too small.  *n_rows: the checks built (B.cq / B.creq; none in a paged call).
+int object_candidates(Call& c, const CandTab& T, u64* n_rows) {
+  LookupBufs& B = c.B;
+  u64 ccap = std::max<u64>(65536, B.cq.cap()), dcap = T.ns.n ? std::max<u64>(65536, B.dkeys.cap()) : 0;
+  for (;;) {
+    LkCtl h;
+    if (int rc = scan_nodes(c, T, ccap, dcap, &h)) return rc;
+    if (h.dcount > dcap || h.kcount > c.K.cap) {
+      dcap = std::max(dcap, h.dcount);
+      ccap = std::max(ccap, h.ccount);
+      if (h.kcount > c.K.cap)
+        if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
+      continue;
+    }
+    if (h.ccount <= ccap && h.dcount)
+      if (int rc = scan_domain(c, T, ccap, (size_t)h.dcount, &h)) return rc;
+    if (h.ccount > ccap) {
+      ccap = h.ccount;
+      continue;
+    }
+    if (h.kcount > c.K.cap) {  // a paged call: the domain's keys did not fit
+      if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
+      continue;
+    }
+    *n_rows = h.ccount;
+    c.K.have = h.kcount;
+    return 0;
+  }
+}
+
+// The end of an unpaged call: the formula requests' candidate keys, one of each, as rows behind the scan's
+// n_rows; every row through the check, the answers collected, the output.
+int unpaged_objects_tail(Call& c, u64 n_rows, kg_lookup_buf* out) {
+  LookupBufs& B = c.B;
+  const u64* uk;
+  u64 m;
+  if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
+  if (int rc = keep_grow(c, B.cq, (size_t)n_rows, (size_t)(n_rows + m))) return rc;
+  if (int rc = keep_grow(c, B.creq, (size_t)n_rows, (size_t)(n_rows + m))) return rc;
+  auto key_rows = [&](u64, u64) -> int {  // the scan has built the others
+    if (m) launch_key_rows<false, false>(c, uk, m, B.cq.get() + n_rows, B.creq.get() + n_rows);
+    return 0;
+  };
+  if (int rc = confirm<false>(c, n_rows + m, CHUNK_OBJECTS, true, key_rows, ErrCount{B.n_errors.get(), B.errmin.get()}))
+    return rc;
+  return c.finish(out);
+}
+
+// ------------------------------------------------------------------ host: the steps of a subject lookup
+// The plan: the walk's bits (walk mode: the root; formula mode: one per root of a walk leaf, *any_formula)
+// and the confirm-mode requests.
+void plan_subjects(Call& c, const kg_lookup_subj* reqs, const SReq* sr, std::vector<GReq>* greq, std::vector<uint32_t>* conf,
+                   bool* any_formula) {
+  const uint32_t nn = c.s->ds.n_nodes;
+  for (size_t i = 0; i < c.n; i++) {
+    if (sr[i].mode == LS_WALK && sr[i].root < nn)
+      greq->push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root, 0, {}});
+    else if (sr[i].mode == LS_FORMULA) {
+      for (uint32_t t = 0; t < sr[i].n_froot && t < (uint32_t)FP_LEAVES; t++)
+        if (sr[i].froot[t] < nn) {
+          greq->push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].froot[t], 0, {}});
+          *any_formula = true;
+        }
+    } else if (sr[i].mode == LS_CONFIRM) conf->push_back((uint32_t)i);
+  }
+}
+
+// The domain of the confirmation, dom[0, *n_dom): the subject ids that occur in a tuple, one of each --
+// ascending when listed from the check rows csub[0, n_rows) or for a paged call, which indexes it by id (the
+// bitmap's distinct ids come in the order its waves reserved their entries).
+int subject_domain(Call& c, const uint32_t* csub, u64 n_rows, const uint32_t** dom, u64* n_dom) {
+  LookupBufs& B = c.B;
+  const DevSnap& ds = c.s->ds;
+  const bool bits = ds.hbits && !c.s->lookup_domain_rows;
+  u64 dcap = std::max<u64>(65536, B.dom.cap());
+  for (;;) {
+    HIPC(B.dom.reserve((size_t)dcap));
+    HIPC(hipMemsetAsync(&B.ctl.get()->dcount, 0, 8, c.st));
+    if (bits)
+      hipLaunchKernelGGL(k_ls_dom_bits, dim3(std::min(c.grid_wide, ds.hbits_n / 8192 + 1)), dim3(256), 0, c.st, ds.hbits,
+                         ds.hbits_n, B.dom.get(), dcap, B.ctl.get());
+    else
+      hipLaunchKernelGGL(k_ls_dom_rows, c.grid(n_rows), dim3(256), 0, c.st, csub, n_rows, B.dom.get(), dcap,
+                         B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    if (h.dcount > dcap) {
+      dcap = h.dcount;
+      continue;
+    }
+    *n_dom = h.dcount;
+    break;
+  }
+  *dom = B.dom.get();
+  if (!bits && *n_dom)  // an id per row entry that holds it: sort, one of each
+    return sort_keys(c, B.dom, B.dom2, (size_t)*n_dom, 31, dom, n_dom);
+  if (bits && *n_dom && c.pg) return sort_keys(c, B.dom, B.dom2, (size_t)*n_dom, 32, dom, (u64*)nullptr);
+  return 0;
+}
+
+// The end of an unpaged call: every (subject id of the domain, confirm request) pair, subject-id-major, then
+// the formula requests' candidate keys, one of each, through the check in chunks; the output.
+int unpaged_subjects_tail(Call& c, const std::vector<uint32_t>& conf, const uint32_t* dom, u64 n_dom, kg_lookup_buf* out) {
+  LookupBufs& B = c.B;
+  const ErrCount sink{B.n_errors.get(), B.errmin.get()};
+  if (n_dom) {
+    const uint32_t C = (uint32_t)conf.size();
+    HIPC(B.tab.reserve(C));
+    HIPC(hipMemcpyAsync(B.tab.get(), conf.data(), (size_t)C * 4, hipMemcpyHostToDevice, c.st));
+    HIPC(hipStreamSynchronize(c.st));  // conf is pageable
+    auto pair_rows = [&](u64 at, u64 m) -> int {
+      hipLaunchKernelGGL(k_ls_cands, c.grid(m), dim3(256), 0, c.st, dom, n_dom, (const uint32_t*)B.tab.get(), C,
+                         (const kg_lookup_subj*)B.d_req.get(), at, m, B.cq.get(), B.creq.get());
+      return 0;
+    };
+    if (int rc = confirm<true>(c, n_dom * C, CHUNK_SUBJECTS, false, pair_rows, sink)) return rc;
+  }
+  const u64* uk;
+  u64 nk;
+  if (int rc = unique_cand_keys(c, &uk, &nk)) return rc;
+  auto key_rows = [&](u64 at, u64 m) -> int {
+    launch_key_rows<true, false>(c, uk + at, m, B.cq.get(), B.creq.get());
+    return 0;
+  };
+  if (int rc = confirm<true>(c, nk, CHUNK_SUBJECTS, false, key_rows, sink)) return rc;
+  return c.finish(out);
+}
+
 }  // namespace
 
 void lookup_bufs_free(void* p) { delete static_cast<LookupBufs*>(p); }
 
 // kg_lookup_objects on lane L (its stream and workspace; the caller holds the workspace's mutex).  pages:
 // kg_lookup_objects_page -- the same steps, with the candidates as keys checked in rounds, into pout.
-static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n, int32_t gmax,
-                      kg_lookup_buf* out, kg_lookup_pages* pout) {
+static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n,
+                             int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
   Call c(s, L, gmax);
   c.pg = pages;
-  const bool paged = pages != nullptr;
-  LookupBufs& B = c.B;
-  hipStream_t st = c.st;
-  const DevSnap& ds = s->ds;
   const LReq* lr = nullptr;
   const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &lr, [&](uint32_t blocks, const kg_lookup* d_req, LReq* d_lr) {
-        hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, st, ds, formula ? s->d_fidx : nullptr,
+        hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, c.st, s->ds, formula ? s->d_fidx : nullptr,
                            (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, (uint64_t)s->n_check_rows, d_lr);
       }))
     return rc;
-
-  // ---- plan: walk groups and candidate tables
-  std::vector<GReq> greq;
-  std::map<u64, std::vector<uint32_t>> by_key, by_fkey;
-  std::map<uint32_t, std::vector<uint32_t>> by_ns;
-  for (size_t i = 0; i < n; i++) {
-    if (lr[i].mode == LK_ALL) {
-      by_ns[reqs[i].ns].push_back((uint32_t)i);
-      continue;
-    }
-    if (lr[i].mode == LK_FORMULA) {
-      if (lr[i].plan >= s->h_fplans.size()) return set_error(-1, "lookup: formula plan out of range");
-      const FPlan& P = s->h_fplans[lr[i].plan];
-      // the walk listens to the walk leaves; the scan takes the relation and every leaf
-      GReq g{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 0, {}};
-      by_fkey[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
-      for (uint32_t j = 0; j < P.n_leaves && j < (uint32_t)FP_LEAVES; j++) {
-        by_fkey[((u64)reqs[i].ns << 32) | P.leaf[j]].push_back((uint32_t)i);
-        if ((P.walk_leaves >> j) & 1u) g.listen[g.n_listen++] = P.leaf[j];
-      }
-      if (lr[i].hcount && g.n_listen) greq.push_back(g);
-      continue;
-    }
-    if (lr[i].mode == LK_REVERSE && lr[i].hcount)
-      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, 0, 1, {reqs[i].rel}});
-    // candidates of a reverse request: impure nodes -- none without node flags
-    if (lr[i].mode == LK_NODES || ds.nflags) by_key[((u64)reqs[i].ns << 32) | reqs[i].rel].push_back((uint32_t)i);
-  }
-  if (paged) {
-    for (GReq& g : greq) g.from = pages[g.req].from;
-    if (int rc = c.page_upload({})) return rc;
-  }
-  if (!by_fkey.empty() || (paged && (!by_key.empty() || !by_ns.empty())))
+  ObjPlan P;
+  if (int rc = plan_objects(c, reqs, lr, &P)) return rc;
+  if (pages)
+    if (int rc = c.page_upload(P.greq, {})) return rc;
+  // the formula requests' candidates are keys; a paged call's all are
+  if (!P.by_frel.empty() || (pages && (!P.by_rel.empty() || !P.by_ns.empty())))
     if (int rc = c.want_cand_keys()) return rc;
-  if (int rc = walk_groups(c, greq, ReverseWalk{lr})) return rc;
-
-  // ---- candidates: one pass over the nodes, then the sorted domains of the confirm-all namespaces
-  if (!by_key.empty() || !by_ns.empty() || !by_fkey.empty()) {
-    std::vector<uint32_t> blob;
-    const uint32_t K = (uint32_t)by_key.size(), M = (uint32_t)by_ns.size(), FK = (uint32_t)by_fkey.size();
-    // layout (u32 words): keys[2K] | fkeys[2FK] | kall[K] | koff[K+1] | kreq[..] | nsv[M] | nsoff[M+1] | nsreq[..]
-    //                     | fall[FK] | foff[FK+1] | freq[..]
-    std::vector<u64> keys, fkeys;
-    std::vector<uint32_t> kall, koff{0}, kreq, nsv, nsoff{0}, nsreq, fall, foff{0}, freq;
-    for (auto& kv : by_fkey) {
-      fkeys.push_back(kv.first);
-      // every node of a request's own relation (its rows join the answer), the impure nodes of a leaf
-      bool own = false;
-      for (uint32_t r : kv.second) own |= reqs[r].rel == (uint32_t)kv.first;
-      fall.push_back(own ? 1u : 0u);
-      freq.insert(freq.end(), kv.second.begin(), kv.second.end());
-      foff.push_back((uint32_t)freq.size());
-    }
-    for (auto& kv : by_key) {
-      keys.push_back(kv.first);
-      kall.push_back(lr[kv.second[0]].mode == LK_NODES ? 1u : 0u);
-      kreq.insert(kreq.end(), kv.second.begin(), kv.second.end());
-      koff.push_back((uint32_t)kreq.size());
-    }
-    for (auto& kv : by_ns) {
-      nsv.push_back(kv.first);
-      nsreq.insert(nsreq.end(), kv.second.begin(), kv.second.end());
-      nsoff.push_back((uint32_t)nsreq.size());
-    }
-    blob.resize(2 * ((size_t)K + FK));
-    if (K) memcpy(blob.data(), keys.data(), (size_t)K * 8);
-    if (FK) memcpy(blob.data() + 2 * (size_t)K, fkeys.data(), (size_t)FK * 8);
-    auto put = [&blob](const std::vector<uint32_t>& v) {
-      blob.insert(blob.end(), v.begin(), v.end());
-      return blob.size() - v.size();
-    };
-    const size_t o_kall = put(kall), o_koff = put(koff), o_kreq = put(kreq), o_nsv = put(nsv), o_nsoff = put(nsoff),
-                 o_nsreq = put(nsreq), o_fall = put(fall), o_foff = put(foff), o_freq = put(freq);
-    blob.push_back(0);
-    HIPC(B.tab.reserve(blob.size() + 2));
-    HIPC(hipMemcpyAsync(B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipStreamSynchronize(st));  // blob is pageable
-    const uint32_t* tb = B.tab.get();
-    const CandTab T{(const u64*)tb, tb + o_kall, tb + o_koff, tb + o_kreq, K, tb + o_nsv, tb + o_nsoff, tb + o_nsreq, M,
-                    (const u64*)tb + K, tb + o_fall, tb + o_foff, tb + o_freq, FK};
-    const kg_lookup* d_req = (const kg_lookup*)B.d_req.get();
-    u64 ccap = std::max<u64>(65536, B.cq.cap()), dcap = M ? std::max<u64>(65536, B.dkeys.cap()) : 0;
-    for (;;) {
-      HIPC(B.cq.reserve((size_t)ccap));
-      HIPC(B.creq.reserve((size_t)ccap));
-      if (dcap) HIPC(B.dkeys.reserve((size_t)dcap));
-      HIPC(hipMemsetAsync(&B.ctl.get()->ccount, 0, 16, st));  // ccount, dcount
-      if (FK || paged)  // the candidate keys back at the walk's
-        if (int rc = c.rewind()) return rc;
-      const dim3 sgrid(std::max(1u, std::min(c.grid_wide, ds.n_nodes / 256 + 1)));
-      const PgReq* d_pg = B.pst.get();
-      if (paged)
-        hipLaunchKernelGGL(k_lk_scan<true>, sgrid, dim3(256), 0, st, ds, T, d_req, B.cq.get(), B.creq.get(), ccap,
-                           B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
-      else
-        hipLaunchKernelGGL(k_lk_scan<false>, sgrid, dim3(256), 0, st, ds, T, d_req, B.cq.get(), B.creq.get(), ccap,
-                           B.dkeys.get(), dcap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
-      HIPC(hipGetLastError());
-      LkCtl h;
-      if (int rc = c.read_ctl(&h)) return rc;
-      if (h.dcount > dcap || h.kcount > c.K.cap) {
-        dcap = std::max(dcap, h.dcount);
-        ccap = std::max(ccap, h.ccount);
-        if (h.kcount > c.K.cap)
-          if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
-        continue;
-      }
-      if (h.ccount <= ccap && h.dcount) {
-        const size_t nd = (size_t)h.dcount;
-        const u64* dk = nullptr;
-        if (int rc = sort_keys(c, B.dkeys, B.dkeys2, nd, 64, &dk, (u64*)nullptr)) return rc;
-        const dim3 dgrid((uint32_t)std::min<u64>(c.grid_wide, nd / 256 + 1));
-        if (paged)
-          hipLaunchKernelGGL(k_lk_domain<true>, dgrid, dim3(256), 0, st, T, dk, (u64)nd, d_req, B.cq.get(), B.creq.get(),
-                             ccap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
-        else
-          hipLaunchKernelGGL(k_lk_domain<false>, dgrid, dim3(256), 0, st, T, dk, (u64)nd, d_req, B.cq.get(), B.creq.get(),
-                             ccap, B.kkeys.get(), c.K.cap, d_pg, B.ctl.get());
-        HIPC(hipGetLastError());
-        if (int rc = c.read_ctl(&h)) return rc;
-      }
-      if (h.ccount > ccap) {
-        ccap = h.ccount;
-        continue;
-      }
-      if (h.kcount > c.K.cap) {  // a paged call: the domain's keys did not fit
-        if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
-        continue;
-      }
-      c.n_cand = h.ccount;
-      c.K.have = h.kcount;
-      break;
-    }
+  if (int rc = walk_groups(c, P.greq, ReverseWalk{lr})) return rc;
+  u64 n_rows = 0;
+  if (P.tables()) {
+    CandTab T;
+    if (int rc = upload_tables(c, P, reqs, lr, &T)) return rc;
+    if (int rc = object_candidates(c, T, &n_rows)) return rc;
   }
-  // ---- a paged call: every candidate is a key; one of each, checked in ascending rounds
-  if (paged) {
-    const u64* uk = nullptr;
-    u64 m = 0;
-    if (c.K.have)
-      if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
-    if (int rc = (page_rounds<false, kg_lookup>(c, uk, m, nullptr, 0, false))) return rc;
-    return c.finish_page(pout, uk, nullptr);
-  }
-  // ---- the formula requests' candidate keys, one of each, as checks behind the others
-  if (c.K.have) {
-    const u64* uk = nullptr;
-    u64 m = 0;
-    if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
-    if (int rc = keep_grow(c, B.cq, (size_t)c.n_cand, (size_t)(c.n_cand + m))) return rc;
-    if (int rc = keep_grow(c, B.creq, (size_t)c.n_cand, (size_t)(c.n_cand + m))) return rc;
-    hipLaunchKernelGGL((k_lk_key_cands<false, kg_lookup>), dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)),
-                       dim3(256), 0, st, uk, m, (const kg_lookup*)B.d_req.get(), (uint32_t)n, B.cq.get() + c.n_cand,
-                       B.creq.get() + c.n_cand);
-    HIPC(hipGetLastError());
-    c.n_cand += m;
-  }
-  if (c.n_cand) {
-    HIPC(B.cout.reserve((size_t)c.n_cand));
-    HIPC(B.cerr.reserve((size_t)c.n_cand));
-    constexpr u64 CHUNK = 1ull << 28;
-    for (u64 at = 0; at < c.n_cand; at += CHUNK) {
-      const size_t m = (size_t)std::min(CHUNK, c.n_cand - at);
-      if (int rc = check_batch_device(s, c.w, B.cq.get() + at, m, c.gmax, B.cout.get() + at, B.cerr.get() + at, nullptr))
-        return rc;
-    }
-    if (int rc = collect<false>(c, c.n_cand)) return rc;
-  }
-  return c.finish(out);
+  if (pages) return paged_tail<false>(c, nullptr, 0, false, pout);
+  return unpaged_objects_tail(c, n_rows, out);
 }
 
 // kg_lookup_subjects on lane L (as lookup_objects).  Walk-mode requests are listed by the forward walk,
 // 64 bits per group; formula-mode requests take a bit per walk-leaf root there, and what those list is
-// checked; the others by a check of every subject id of the domain, in chunks of CHUNK pairs.
+// checked; the others by a check of every subject id of the domain.
 static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
-                       int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
+                              int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
   Call c(s, L, gmax);
   c.pg = pages;
-  const bool paged = pages != nullptr;
-  LookupBufs& B = c.B;
-  hipStream_t st = c.st;
   const DevSnap& ds = s->ds;
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
   const uint64_t n_rows = s->n_check_rows;
   const SReq* sr = nullptr;
   const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj* d_req, SReq* d_sr) {
-        hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, st, ds, formula ? s->d_fidx : nullptr,
+        hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, c.st, ds, formula ? s->d_fidx : nullptr,
                            (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, d_sr);
       }))
     return rc;
-
-  std::vector<GReq> greq;      // walk and formula mode, by group and bit
-  std::vector<uint32_t> conf;  // confirm mode
+  std::vector<GReq> greq;
+  std::vector<uint32_t> conf;
   bool any_formula = false;
-  for (size_t i = 0; i < n; i++) {
-    if (sr[i].mode == LS_WALK && sr[i].root < ds.n_nodes)
-      greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root, 0, {}});
-    else if (sr[i].mode == LS_FORMULA) {  // one bit per root of a walk leaf
-      for (uint32_t t = 0; t < sr[i].n_froot && t < (uint32_t)FP_LEAVES; t++)
-        if (sr[i].froot[t] < ds.n_nodes) {
-          greq.push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].froot[t], 0, {}});
-          any_formula = true;
-        }
-    } else if (sr[i].mode == LS_CONFIRM) conf.push_back((uint32_t)i);
-  }
-  if (paged) {
+  plan_subjects(c, reqs, sr, &greq, &conf, &any_formula);
+  if (pages) {  // the confirm requests index the domain, the formula requests their unique keys
     std::vector<uint8_t> implicit(n, 0);
     for (uint32_t r : conf) implicit[r] = 1;
-    for (GReq& g : greq) g.from = pages[g.req].from;
-    if (int rc = c.page_upload(implicit)) return rc;
+    if (int rc = c.page_upload(greq, implicit)) return rc;
   }
   if (any_formula)
     if (int rc = c.want_cand_keys()) return rc;
   if (int rc = walk_groups(c, greq, ForwardWalk{sr, Rows{ds.crow_off ? ds.crow_off : ds.row_off, csub, n_rows}})) return rc;
-
-  // ---- confirmation: the domain once, then every (subject id, request) pair through the check
   u64 n_dom = 0;
   const uint32_t* dom = nullptr;
-  if (!conf.empty() && n_rows && csub) {
-    const bool bits = ds.hbits && !s->lookup_domain_rows;
-    u64 dcap = std::max<u64>(65536, B.dom.cap());
-    for (;;) {
-      HIPC(B.dom.reserve((size_t)dcap));
-      HIPC(hipMemsetAsync(&B.ctl.get()->dcount, 0, 8, st));
-      if (bits)
-        hipLaunchKernelGGL(k_ls_dom_bits, dim3(std::min(c.grid_wide, ds.hbits_n / 8192 + 1)), dim3(256), 0, st, ds.hbits,
-                           ds.hbits_n, B.dom.get(), dcap, B.ctl.get());
-      else
-        hipLaunchKernelGGL(k_ls_dom_rows, dim3((uint32_t)std::min<u64>(c.grid_wide, n_rows / 256 + 1)), dim3(256), 0, st,
-                           csub, (u64)n_rows, B.dom.get(), dcap, B.ctl.get());
-      HIPC(hipGetLastError());
-      LkCtl h;
-      if (int rc = c.read_ctl(&h)) return rc;
-      if (h.dcount > dcap) {
-        dcap = h.dcount;
-        continue;
-      }
-      n_dom = h.dcount;
-      break;
-    }
-    dom = B.dom.get();
-    if (!bits && n_dom)  // an id per row entry that holds it: sort, one of each
-      if (int rc = sort_keys(c, B.dom, B.dom2, (size_t)n_dom, 31, &dom, &n_dom)) return rc;
-    // the bitmap's ids are distinct but come in the order its waves reserved their entries: a paged call
-    // indexes the domain by id
-    if (bits && n_dom && paged)
-      if (int rc = sort_keys(c, B.dom, B.dom2, (size_t)n_dom, 32, &dom, (u64*)nullptr)) return rc;
-  }
-  // ---- a paged call: the confirm requests index the domain, the formula requests their unique keys
-  if (paged) {
-    const u64* uk = nullptr;
-    u64 m = 0;
-    if (c.K.have)
-      if (int rc = unique_cand_keys(c, &uk, &m)) return rc;
-    if (int rc = (page_rounds<true, kg_lookup_subj>(c, uk, m, dom, n_dom, !conf.empty()))) return rc;
-    return c.finish_page(pout, uk, dom);
-  }
-  if (n_dom) {
-    const uint32_t C = (uint32_t)conf.size();
-    HIPC(B.tab.reserve(C));
-    HIPC(hipMemcpyAsync(B.tab.get(), conf.data(), (size_t)C * 4, hipMemcpyHostToDevice, st));
-    HIPC(hipStreamSynchronize(st));  // conf is pageable
-    c.n_cand = n_dom * C;
-    constexpr u64 CHUNK = 1ull << 22;
-    const size_t ccap = (size_t)std::min(CHUNK, c.n_cand);
-    HIPC(B.cq.reserve(ccap));
-    HIPC(B.creq.reserve(ccap));
-    HIPC(B.cout.reserve(ccap));
-    HIPC(B.cerr.reserve(ccap));
-    for (u64 at = 0; at < c.n_cand; at += CHUNK) {
-      const u64 m = std::min(CHUNK, c.n_cand - at);
-      hipLaunchKernelGGL(k_ls_cands, dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)), dim3(256), 0, st, dom, n_dom,
-                         (const uint32_t*)B.tab.get(), C, (const kg_lookup_subj*)B.d_req.get(), at, m, B.cq.get(),
-                         B.creq.get());
-      HIPC(hipGetLastError());
-      if (int rc = check_batch_device(s, c.w, B.cq.get(), (size_t)m, c.gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;
-      if (int rc = collect<true>(c, m)) return rc;
-    }
-  }
-  // ---- the formula requests' candidate keys, one of each, through the check in the same chunks
-  if (c.K.have) {
-    const u64* uk = nullptr;
-    u64 nk = 0;
-    if (int rc = unique_cand_keys(c, &uk, &nk)) return rc;
-    c.n_cand += nk;
-    constexpr u64 CHUNK = 1ull << 22;
-    const size_t ccap = (size_t)std::min(CHUNK, nk);
-    HIPC(B.cq.reserve(ccap));
-    HIPC(B.creq.reserve(ccap));
-    HIPC(B.cout.reserve(ccap));
-    HIPC(B.cerr.reserve(ccap));
-    for (u64 at = 0; at < nk; at += CHUNK) {
-      const u64 m = std::min(CHUNK, nk - at);
-      hipLaunchKernelGGL((k_lk_key_cands<true, kg_lookup_subj>), dim3((uint32_t)std::min<u64>(c.grid_wide, m / 256 + 1)),
-                         dim3(256), 0, st, uk + at, m, (const kg_lookup_subj*)B.d_req.get(), (uint32_t)n, B.cq.get(),
-                         B.creq.get());
-      HIPC(hipGetLastError());
-      if (int rc = check_batch_device(s, c.w, B.cq.get(), (size_t)m, c.gmax, B.cout.get(), B.cerr.get(), nullptr)) return rc;
-      if (int rc = collect<true>(c, m)) return rc;
-    }
-  }
-  return c.finish(out);
+  if (!conf.empty() && n_rows && csub)
+    if (int rc = subject_domain(c, csub, n_rows, &dom, &n_dom)) return rc;
+  if (pages) return paged_tail<true>(c, dom, n_dom, !conf.empty(), pout);
+  return unpaged_subjects_tail(c, conf, dom, n_dom, out);
 }
 
 int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {

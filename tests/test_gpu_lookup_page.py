@@ -10,6 +10,7 @@ page's last id + 1; n_errors / err_code are about the ids of E in [frm, next).
   5  the early stop: checks <= sum of max(64, 4 c*) (derived in test_early_stop_*)
   6  walk keys and confirmed candidates interleaved
   7  refresh, threads, engine and handlers
+  8  one call with requests of every mode, unpaged and paged, lists at their default size and at 64 entries
 """
 import threading
 
@@ -651,3 +652,90 @@ def test_sharded_snapshot_is_refused():
     assert "(-3)" in str(ex.value)
     with pytest.raises(_lib.KetoGPUError, match="limit 0"):
         Engine(snap, Config(5)).lookup_objects_page_ids(reqs[:1], [[0, 0]])
+
+
+# ---------------------------------------------------------------- 8. every tail through the shared confirm step
+def _mixed_case():
+    """Two namespaces, about 320 objects.  d: a, b and blocked are plain (reverse mode / walk), share = a and not
+    blocked is a formula over plain leaves, open = not blocked has f(0) = true (confirm-all, with members) and
+    nope is undeclared (confirm-all, every id errs).  The nodes d:o250..o259#a hold a subject set that reaches
+    the rewrite share, so they are impure: candidates of the reverse requests and confirm-mode roots.  Returns
+    the requests with the mode each takes, interleaved, one of them twice."""
+    it = Interner()
+    C, N, O = ComputedSubjectSet, InvertResult, SubjectSetRewrite
+    namespaces = [Namespace("d", [Relation("a"), Relation("b"), Relation("blocked"),
+                                  Relation("share", rewrite=O([C("a"), N(C("blocked"))], "and")),
+                                  Relation("open", rewrite=O([N(C("blocked"))]))]),
+                  Namespace("g", [Relation("m")])]
+    tuples = [T(f"d:o{i}#a@big") for i in range(200)] + [T(f"d:o{i}#a@alice") for i in range(30)]
+    tuples += [T(f"d:o{i}#b@alice") for i in range(300, 310)]
+    tuples += [T(f"d:o{i}#blocked@alice") for i in (3, 4, 100)] + [T(f"d:o{i}#blocked@big") for i in range(150, 160)]
+    tuples += [T(f"d:o{i}#a@(d:z#share)") for i in range(250, 260)] + [T("d:z#a@carol"), T("d:z#a@big")]
+    tuples += [T(f"d:hub#a@s{i}") for i in range(100)] + [T("d:hub#blocked@s5"), T("d:hub#blocked@s6")]
+    tuples += [T(f"g:t{k}#m@alice") for k in range(10)] + [T(f"g:t{k}#m@(g:core#m)") for k in range(5, 90)]
+    tuples += [T("g:core#m@big")]
+    oq = [("reverse", "d:any#a@big"), ("formula", "d:any#share@alice"), ("all", "d:any#open@alice"),
+          ("all", "d:any#nope@alice"), ("reverse", "d:any#a@carol"), ("formula", "d:any#share@big"),
+          ("all", "d:any#open@big"), ("reverse", "g:any#m@big"), ("all", "d:any#nope@big"),
+          ("reverse", "d:any#a@big"), ("formula", "d:any#share@carol"), ("reverse", "g:any#m@alice")]
+    sq = [("walk", ("d", "hub", "a")), ("formula", ("d", "hub", "share")), ("confirm", ("d", "hub", "open")),
+          ("confirm", ("d", "hub", "nope")), ("walk", ("d", "o1", "a")), ("formula", ("d", "o1", "share")),
+          ("confirm", ("d", "o251", "a")), ("walk", ("g", "t7", "m")), ("confirm", ("d", "o1", "open")),
+          ("walk", ("d", "hub", "a")), ("formula", ("d", "o150", "share")), ("confirm", ("d", "o1", "nope"))]
+    prog = compile_program(namespaces, it, lower_ttu=False)
+    t6 = it.tuples_array(tuples)
+    oreq = lo.requests_array(it, [T(q) for _, q in oq], [0] * len(oq))
+    sreq = ls.requests_array(it, [r for _, r in sq], [0] * len(sq))
+    return it, namespaces, prog, tuples, t6, (oreq, [m for m, _ in oq]), (sreq, [m for m, _ in sq])
+
+
+def _mixed_reference(prog, it, t6, oreq, omodes, sreq, smodes, gmax=5):
+    """The oracle's members and erring ids per request, and the conditions that keep the test from passing
+    vacuously: every mode lists something, some request errs, some answer is longer than the tuned lists."""
+    oracle = Oracle(t6, it.wildcard_rel, prog)
+    ofull = full_objects(oracle, lo.domains(t6), oreq, gmax)
+    sfull = full_subjects(oracle, ls.subject_domain(t6), sreq, gmax)
+    for full, modes in ((ofull, omodes), (sfull, smodes)):
+        for mode in set(modes):
+            assert sum(m == mode for m in modes) >= 2
+            assert any(len(f[0]) for f, m in zip(full, modes) if m == mode), mode
+        assert any(len(f[1]) for f in full)
+        assert max(len(f[0]) for f in full) > 64
+    return ofull, sfull
+
+
+@pytest.fixture(scope="module")
+def mixed():
+    it, namespaces, prog, tuples, t6, (oreq, omodes), (sreq, smodes) = _mixed_case()
+    ofull, sfull = _mixed_reference(prog, it, t6, oreq, omodes, sreq, smodes)
+    reg = Registry(tuples, namespaces, interner=it)
+    yield reg, (oreq, omodes, ofull), (sreq, smodes, sfull)
+    reg.snapshot.tune("lookup_cap", 0)
+
+
+@pytest.mark.parametrize("kind", ["objects", "subjects"])
+def test_every_tail_in_one_call(mixed, kind):
+    """One call holds requests of every mode, so the scan's rows, the domain pairs, the formula keys and the
+    paged rounds all pass through the same confirmation: unpaged against the oracle, the full-limit paged call
+    against the unpaged one, pages of 3 from 0 to END, with the lists at their default size and starting at 64
+    entries (the output list, the candidate keys and the check buffers regrow).  No fixture builds a snapshot
+    without reverse indexes (they are absent only above 2^32 check rows), so the confirm-nodes mode is not run."""
+    reg, ocase, scase = mixed
+    reqs, modes, full = ocase if kind == "objects" else scase
+    e = Engine(reg.snapshot, Config(5))
+    ref = [(f[0], len(f[1]), f[1][0][1] if f[1] else 0) for f in full]
+    counters = []
+    for cap in (0, 64):
+        reg.snapshot.tune("lookup_cap", cap)
+        seen = []
+
+        def note(live=None):
+            seen.append((e.last_stats["candidates"], e.last_stats["confirmed"]))
+
+        (lo if kind == "objects" else ls).compare(e, reqs, ref)
+        note()
+        assert seen[0][0] > 0 and seen[0][1] > 0 and 0 < e.last_stats["exact"] < e.last_stats["n_objs"], e.last_stats
+        _identity(e, kind, reqs)
+        page_through(objects_call(e) if kind == "objects" else subjects_call(e), reqs, 3, full, stats=note)
+        counters.append(seen)
+    assert counters[0] == counters[1]
