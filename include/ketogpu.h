@@ -683,6 +683,38 @@ typedef struct {
 int kg_lookup_subjects(kg_snapshot* s, const kg_lookup_subj* reqs, size_t n, int32_t global_max_depth,
                        kg_lookup_buf* out);
 
+/* "Which subject sets sns:*#srel may do rel on ns:obj?" -- which groups (group:*#member) have access to
+ * this document, directly or through nesting (OpenFGA ListUsers with a user filter {type, relation};
+ * SpiceDB LookupSubjects with subject_object_type and optional_subject_relation).  The domain of a request
+ * is the object ids o for which the subject set sns:o#srel occurs as the subject of at least one tuple of
+ * the snapshot (kg_snapshot_export's rows; `...` sets are sets like any other; a set that exists only as an
+ * object is not in it, and after kg_snapshot_apply neither is a set whose last holding tuple was deleted).
+ * The answer is the ascending o of the domain for which a check of ns:obj#rel@(sns:o#srel) with max_depth
+ * and the call's global_max_depth answers KG_IS_MEMBER.  An o whose check answers KG_ERROR is not listed:
+ * n_errors[i] counts them and err_code[i] is the code of the lowest -- an undeclared rel lists nothing and
+ * reports every set of the domain.  A filter no tuple's subject matches (ids out of range, a namespace
+ * the snapshot has never seen) is an empty answer, not an error.
+ * sns == KG_SUBJECT_ID: the request lists subject ids instead (srel is ignored) and returns
+ * kg_lookup_subjects' answer for (ns, obj, rel, max_depth) -- ids, n_errors and err_code.  One call may mix
+ * id requests and set requests, and requests with different filters.
+ * How: the request modes are kg_lookup_subjects' and do not depend on the filter.  The forward walk's one
+ * pass over the check rows lists both kinds of entry: an untagged one to the requests that ask for ids, a
+ * tagged one (a subject set's node) to the requests whose filter is that node's (namespace, relation); a
+ * walk group without a set request runs kg_lookup_subjects' code.  A formula request's walk lists its
+ * candidate sets the same way.  A request that is answered by checks takes its filter's domain: one scan of
+ * the check rows per call lists the sets of the call's distinct filters, sorted and made unique, and every
+ * one is checked for every such request of that filter (domain x requests checks).
+ * The output is a kg_lookup_buf as for kg_lookup_subjects, with "id" read as "listed object id of a set".
+ * Thread-safety, lanes, the replica rotation, hash-sharded snapshots (-3), "lookup_cap" and
+ * "lookup_formula" as kg_lookup_subjects. */
+typedef struct {
+  uint32_t ns, obj, rel; /* the object and the relation asked for */
+  uint32_t sns, srel;    /* list the subject sets sns:*#srel; sns = KG_SUBJECT_ID: list subject ids (srel ignored) */
+  int32_t max_depth;     /* <= 0: the global depth */
+} kg_lookup_subj_set;    /* 24 bytes */
+int kg_lookup_subject_sets(kg_snapshot* s, const kg_lookup_subj_set* reqs, size_t n, int32_t global_max_depth,
+                           kg_lookup_buf* out);
+
 /* ---- paged lookups ----------------------------------------------------------------------- */
 /* The next `limit` ids of a lookup's answer from a cursor (OpenFGA ListObjects caps its result; SpiceDB
  * LookupResources / LookupSubjects take a cursor and a limit).  The page is defined through the unpaged
@@ -720,6 +752,10 @@ int kg_lookup_objects_page(kg_snapshot* s, const kg_lookup* reqs, const kg_looku
                            int32_t global_max_depth, kg_lookup_pages* out);
 int kg_lookup_subjects_page(kg_snapshot* s, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
                             int32_t global_max_depth, kg_lookup_pages* out);
+/* kg_lookup_subject_sets paged, defined through the unpaged call as above.  A request answered by checks
+ * takes its filter's sets at or above `from` as explicit candidate keys (request, id). */
+int kg_lookup_subject_sets_page(kg_snapshot* s, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages,
+                                size_t n, int32_t global_max_depth, kg_lookup_pages* out);
 void kg_lookup_pages_free(kg_lookup_pages* out);
 
 /* ---- tuple listing ----------------------------------------------------------------------- */

@@ -119,6 +119,12 @@ class kg_lookup_pages(C.Structure):
                 ("pinned", C.c_uint64)]
 
 
+class kg_lookup_subj_set(C.Structure):
+    """A kg_lookup_subject_sets request: list the subject sets sns:*#srel (sns = KG_SUBJECT_ID: subject ids)."""
+    _fields_ = [("ns", C.c_uint32), ("obj", C.c_uint32), ("rel", C.c_uint32), ("sns", C.c_uint32),
+                ("srel", C.c_uint32), ("max_depth", C.c_int32)]
+
+
 KG_Q_NS, KG_Q_OBJ, KG_Q_REL, KG_Q_SUBJECT = 1, 2, 4, 8
 
 
@@ -157,7 +163,8 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
            "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
            "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free",
-           "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free"]
+           "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free",
+           "kg_lookup_subject_sets", "kg_lookup_subject_sets_page"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -245,6 +252,12 @@ def load(path: str = LIB_PATH):
         L.kg_lookup_subjects_page.restype = C.c_int
         L.kg_lookup_pages_free.argtypes = [C.POINTER(kg_lookup_pages)]
         L.kg_lookup_pages_free.restype = None
+    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_subject_sets"):
+        # (an A/B build from before the subject-set lookup goes without it, as above)
+        L.kg_lookup_subject_sets.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
+        L.kg_lookup_subject_sets.restype = C.c_int
+        L.kg_lookup_subject_sets_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
+        L.kg_lookup_subject_sets_page.restype = C.c_int
     L.kg_snapshot_query.argtypes = [vp, vp, sz, C.POINTER(kg_query_buf)]
     L.kg_snapshot_query.restype = C.c_int
     L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]

@@ -1052,6 +1052,15 @@ int kg_lookup_subjects(kg_snapshot* sp, const kg_lookup_subj* reqs, size_t n, in
   KG_GUARD_END
 }
 
+int kg_lookup_subject_sets(kg_snapshot* sp, const kg_lookup_subj_set* reqs, size_t n, int32_t global_max_depth,
+                           kg_lookup_buf* out) {
+  KG_GUARD_BEGIN
+  return lookup_call("kg_lookup_subject_sets", sp, reqs, n, out, false, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_subject_sets(rep, L, reqs, n, global_max_depth, out);
+  });
+  KG_GUARD_END
+}
+
 void kg_lookup_free(kg_lookup_buf* out) {
   if (out) kg::lookup_free(out);
 }
@@ -1082,6 +1091,15 @@ int kg_lookup_subjects_page(kg_snapshot* sp, const kg_lookup_subj* reqs, const k
   KG_GUARD_BEGIN
   return lookup_page_call("kg_lookup_subjects_page", sp, reqs, pages, n, out, [&](Snapshot* rep, kg::Lane* L) {
     return kg::lookup_subjects_page(rep, L, reqs, pages, n, global_max_depth, out);
+  });
+  KG_GUARD_END
+}
+
+int kg_lookup_subject_sets_page(kg_snapshot* sp, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages, size_t n,
+                                int32_t global_max_depth, kg_lookup_pages* out) {
+  KG_GUARD_BEGIN
+  return lookup_page_call("kg_lookup_subject_sets_page", sp, reqs, pages, n, out, [&](Snapshot* rep, kg::Lane* L) {
+    return kg::lookup_subject_sets_page(rep, L, reqs, pages, n, global_max_depth, out);
   });
   KG_GUARD_END
 }

@@ -1,10 +1,14 @@
-// kg_lookup.hip -- the two lookups, neither with a reference counterpart in Keto: the objects of a
+// kg_lookup.hip -- the lookups, none with a reference counterpart in Keto: the objects of a
 // namespace a subject has a relation on (kg_lookup_objects: OpenFGA ListObjects / SpiceDB LookupResources)
-// and the subject ids that hold a relation on one object (kg_lookup_subjects: ListUsers / LookupSubjects).
+// and the subjects that hold a relation on one object (ListUsers / LookupSubjects) -- the subject ids
+// (kg_lookup_subjects) or the subject sets of one namespace and relation, "which group:*#member may view
+// this?" (kg_lookup_subject_sets: ListUsers' user filter {type, relation}; a request of it may ask for ids too).
 //
 // The answer is defined through the check: for a request (ns, rel, subject, max_depth) the ascending
 // object ids o with a node (ns, o, *) for which CheckIsMember(ns:o#rel@subject, max_depth) is IsMember; for
-// (ns, obj, rel, max_depth) the subject ids of tuples with that check on ns:obj#rel.  An object request is
+// (ns, obj, rel, max_depth) the subject ids of tuples with that check on ns:obj#rel; for (ns, obj, rel, sns,
+// srel, max_depth) the object ids o of the subject sets sns:o#srel of tuples -- `...` sets are sets like any
+// other -- with that check of ns:obj#rel@(sns:o#srel).  An object request is
 // answered in one of four modes (k_lk_resolve):
 //   reverse        (ns, rel) has no rewrite or is a materialised union, and the reverse indexes exist:
 //                  every member is a node of (ns, rel); a PURE node is a member iff its reverse distance
@@ -26,11 +30,22 @@
 // walk over adj.  One on a lookup_ok plan whose object has no node of the relation and only pure leaf
 // nodes walks from its J-leaf roots: the ids they list are its candidates (an id none of them lists is
 // NotMember of every J leaf, so of f), made unique and confirmed.  Everything else confirms every
-// subject id.  "Confirmed" = run through check_batch_device as kg_query rows built on the device; no
-// check kernel is touched.  Every confirmation -- the object lookup's candidates, the subject lookup's
-// (subject id, request) pairs, either's formula keys, a paged round -- is one call of confirm(): a launch that
-// builds the rows (all of them through lk_row), the checks in chunks, one collect (k_lk_collect; where the
-// errors go is its sink: counted per request, or listed for a paged call).
+// subject id.  What a subject request lists does not change its mode.  The walk's one pass over the check
+// rows of the nodes it reaches lists both kinds of entry (Emit): an untagged one is a subject id and goes
+// to the bits that ask for ids, a tagged one SET_BIT | v is the subject set of node v and goes to the bits
+// whose filter is (nd_ns[v], nd_rel[v]), which list nd_obj[v]; a group without such a bit (Walk::smask == 0)
+// reads no tagged entry's node.  A set in the row of a node k hops below the root is listed iff k <= D-1, as
+// an id is.  A formula request's walk lists its candidate sets the same way: a set none of the J leaves'
+// walks lists is NotMember of every J leaf.  A request that confirms and lists sets takes the domain of its
+// filter instead of the subject ids: one scan of the check rows per call (k_ls_dom_sets) emits filter slot
+// << 32 | object id for the tagged entries of the call's distinct filters, sorted; every distinct set
+// becomes a candidate key of each such request of that filter (k_lk_domain), checked once next to the
+// formula requests' keys -- domain x requests checks.  "Confirmed" = run through check_batch_device as
+// kg_query rows built on the device; no check kernel is touched.  Every confirmation -- the object lookup's
+// candidates, the subject lookup's (subject id, request) pairs, either's candidate keys, a paged round -- is
+// one call of confirm(): a launch that builds the rows (all of them through lk_row), the checks in chunks,
+// one collect (k_lk_collect; where the errors go is its sink: counted per request, or listed for a paged
+// call).
 //
 // There is one walk (walk_groups) with two direction policies (ReverseWalk, ForwardWalk).  It is level-
 // synchronous and bit-parallel over groups of 64 requests: a dense u64 visited mask per node (bit =
@@ -41,7 +56,7 @@
 // The paged calls (kg_lookup_objects_page / kg_lookup_subjects_page: the first `limit` ids >= `from` of the
 // unpaged answer) run the same steps with three differences.  A walk bit lists no id below its request's
 // cursor (GReq::from).  Every candidate of a confirmation becomes a key request << 32 | id at or above the
-// cursor -- the subject lookup's confirm requests index the ascending domain instead -- and no check is
+// cursor -- the subject lookup's confirm requests for ids index the ascending domain instead -- and no check is
 // built up front: the sorted unique keys are checked in ascending rounds (paged_tail, page_rounds: each round
 // one confirm()), at most 64 of a request first, then at most as many again as it has checked, until
 // limit + 1 of its members (walk keys and confirmed candidates) lie at or below the largest id it has
@@ -103,9 +118,11 @@ struct GReq {
   // reverse walk: the relations of ns the bit listens to -- rel itself, or a formula request's walk leaves
   uint32_t n_listen, listen[FP_LEAVES];
   uint32_t from;  // paged calls: the request's cursor -- the bit lists no id below it
+  // forward walk: what the bit lists -- the subject sets sns:*#srel, or (sns == KG_SUBJECT_ID) subject ids
+  uint32_t sns, srel;
 };
 // A request of a paged call: its page, and its run of candidates -- [lo, hi) of the call's sorted unique
-// candidate keys or, `implicit` (a subject lookup's confirm request), of the ascending subject domain.
+// candidate keys or, `implicit` (a subject lookup's confirm request for ids), of the ascending subject domain.
 // The rounds check [lo, cur); the round being built takes [base, cur).
 struct PgReq {
   u64 lo, hi, cur, base;
@@ -135,6 +152,7 @@ struct Walk {
   const GReq* greq;   // the group's requests, by bit
   LkCtl* ctl;
   bool paged;         // a paged call: a bit lists only the ids at or above its request's cursor
+  u64 smask;          // the group's bits that list subject sets (GReq::sns / srel), not subject ids
 };
 
 // A group table: distinct ascending keys, each with a flag and the requests that share it.
@@ -247,14 +265,15 @@ struct SReq {
 // confirmed.  A relation with a lookup_ok plan (fidx / plans; nullptr: none) whose object has no node of
 // the relation and no impure leaf node -- the condition under which k_fsplit splits its checks -- walks
 // from the object's nodes of the walk leaves, or is empty without one.  Every other relation
-// (interpreter, undeclared) is confirmed.
+// (interpreter, undeclared) is confirmed.  What the request lists (subject ids, or the subject sets of a
+// filter) plays no part.
 __global__ __launch_bounds__(256) void k_ls_resolve(DevSnap s, const int32_t* __restrict__ fidx,
                                                     const FPlan* __restrict__ plans,
-                                                    const kg_lookup_subj* __restrict__ q, uint32_t n, int32_t global,
-                                                    SReq* __restrict__ sr) {
+                                                    const kg_lookup_subj_set* __restrict__ q, uint32_t n,
+                                                    int32_t global, SReq* __restrict__ sr) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const kg_lookup_subj x = q[i];
+  const kg_lookup_subj_set x = q[i];
   uint32_t mode = LS_CONFIRM, root = NONE;
   if (relflag(s, x.ns, x.rel) == 0 || rel_is_union(s, x.ns, x.rel)) {
     root = nmap_find(s, x.ns, x.rel, x.obj);
@@ -484,12 +503,32 @@ struct Hop {
     else lk_mark(s, W, true, p, m & on);
   }
 };
-// The forward walk's emit over the check rows.  An untagged entry is a subject id every request bit of
-// its node lists (request << 32 | id); subject sets -- `...` ones included -- are skipped.  An id the
-// check maps to no subject (>= 2^31 - 1, k_resolve) is never a member.
-struct EmitIds {
+// The forward walk's emit over the check rows.  An untagged entry is a subject id: the id bits of its node
+// list it (request << 32 | id).  An id the check maps to no subject (>= 2^31 - 1, k_resolve) is never a
+// member.  A tagged entry SET_BIT | v is the subject set of node v -- `...` sets are sets like any other --
+// and the set bits whose filter is v's (namespace, relation) list v's object.  A group without a set bit
+// (W.smask == 0, the same for every lane) never looks at a tagged entry.
+struct Emit {
+  DevSnap s;
   Walk W;
-  __device__ void operator()(uint32_t sub, u64 m) const { lk_list(W, sub < 0x7FFFFFFFu ? m : 0ull, sub); }
+  __device__ void operator()(uint32_t sub, u64 m) const {
+    if (!W.smask) {
+      lk_list(W, sub < 0x7FFFFFFFu ? m : 0ull, sub);
+      return;
+    }
+    u64 bits = 0;
+    uint32_t id = sub;
+    if (!(sub & SET_BIT)) bits = sub < 0x7FFFFFFFu ? m & ~W.smask : 0ull;
+    else if ((m & W.smask) && (sub & ~SET_BIT) < s.n_nodes) {  // a lane without an entry has NONE and no bit
+      const uint32_t v = sub & ~SET_BIT, vns = s.nd_ns[v], vrel = s.nd_rel[v];
+      for (u64 b = m & W.smask; b; b &= b - 1) {
+        const GReq& g = W.greq[__ffsll(b) - 1];
+        if (g.sns == vns && g.srel == vrel) bits |= b & -b;
+      }
+      if (bits) id = s.nd_obj[v];
+    }
+    lk_list(W, bits, id);
+  }
 };
 
 // After a group: the masks of every touched node back to 0, the node lists empty.
@@ -508,16 +547,16 @@ __global__ void k_lk_lists_reset(LkCtl* ctl) {
 }
 
 // ------------------------------------------------------------------ check rows
-// SUBJ: a subject lookup (its requests list subject ids), else an object lookup (object ids).
+// SUBJ: a subject lookup (its requests list subject ids or subject sets), else an object lookup (object ids).
 template <bool SUBJ>
-using ReqOf = typename std::conditional<SUBJ, kg_lookup_subj, kg_lookup>::type;
+using ReqOf = typename std::conditional<SUBJ, kg_lookup_subj_set, kg_lookup>::type;
 
-// The check of request x on a candidate id: ns:id#rel@subject of an object lookup's request, ns:obj#rel@id
-// of a subject lookup's.
+// The check of request x on a candidate id: ns:id#rel@subject of an object lookup's request; of a subject
+// lookup's ns:obj#rel@id, or ns:obj#rel@(sns:id#srel) where it lists the subject sets of a filter.
 template <bool SUBJ>
 __device__ __forceinline__ kg_query lk_row(const ReqOf<SUBJ>& x, uint32_t id) {
   kg_query y;
-  if constexpr (SUBJ) y.t = kg_tuple{x.ns, x.obj, x.rel, KG_SUBJECT_ID, id, 0};
+  if constexpr (SUBJ) y.t = kg_tuple{x.ns, x.obj, x.rel, x.sns, id, x.sns == KG_SUBJECT_ID ? 0u : x.srel};
   else y.t = kg_tuple{x.ns, id, x.rel, x.sns, x.sobj, x.srel};
   y.max_depth = x.max_depth;
   return y;
@@ -549,12 +588,31 @@ __global__ __launch_bounds__(256) void k_ls_dom_rows(const uint32_t* __restrict_
   }
 }
 
+// The domain of the confirm requests that list subject sets depends on their filter: every tagged entry
+// SET_BIT | v of the check rows whose (nd_ns[v] << 32 | nd_rel[v]) is one of the call's distinct filters F
+// becomes a domain key filter slot << 32 | nd_obj[v] (sorted next; k_lk_domain pairs the first key of every
+// run with the slot's requests).
+__global__ __launch_bounds__(256) void k_ls_dom_sets(DevSnap s, const uint32_t* __restrict__ csub, u64 n_rows,
+                                                     GroupTab<u64> F, u64* dkeys, u64 dcap, LkCtl* ctl) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 base = (u64)blockIdx.x * 256 + (threadIdx.x & ~63u); base < n_rows; base += stride) {
+    const u64 i = base + lane_id();
+    const uint32_t sub = i < n_rows ? csub[i] : NONE, v = sub & ~SET_BIT;
+    uint32_t slot = NONE, obj = 0;
+    if ((sub & SET_BIT) && v < s.n_nodes) {
+      slot = lk_find(F.keys, F.n, ((u64)s.nd_ns[v] << 32) | s.nd_rel[v]);
+      if (slot != NONE) obj = s.nd_obj[v];
+    }
+    lk_append64(slot != NONE, ((u64)slot << 32) | obj, dkeys, &ctl->dcount, dcap);
+  }
+}
+
 // Candidate checks [at, at + m) of the confirmation: pair p = (subject id p / C of the domain, confirm
 // request p % C) becomes the kg_query ns:obj#rel@id of that request.
 __global__ __launch_bounds__(256) void k_ls_cands(const uint32_t* __restrict__ dom, u64 n_dom,
                                                   const uint32_t* __restrict__ conf, uint32_t C,
-                                                  const kg_lookup_subj* __restrict__ q, u64 at, u64 m, kg_query* cq,
-                                                  uint32_t* creq) {
+                                                  const kg_lookup_subj_set* __restrict__ q, u64 at, u64 m,
+                                                  kg_query* cq, uint32_t* creq) {
   const u64 stride = (u64)gridDim.x * 256;
   for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
     const u64 p = at + i, d = p / C;
@@ -654,7 +712,9 @@ __global__ __launch_bounds__(256) void k_lk_key_rows(const u64* __restrict__ key
 }
 
 // The sorted domain keys: the first key of every run is one object of the namespace; it becomes a check
-// for every confirm-all request of that namespace -- PAGED: a candidate key, as k_lk_scan.
+// for every confirm-all request of that namespace -- PAGED: a candidate key, as k_lk_scan.  The subject
+// lookup's per-filter domains (k_ls_dom_sets) take the PAGED form with T.ns holding the filter slots'
+// requests (pg == nullptr in an unpaged call: no cursor).
 template <bool PAGED>
 __global__ __launch_bounds__(256) void k_lk_domain(CandTab T, const u64* __restrict__ dk, u64 nd,
                                                    const kg_lookup* __restrict__ q, kg_query* cq, uint32_t* creq,
@@ -1399,7 +1459,7 @@ void launch_edges(Call& c, const Frontier& f, const Rows& r, const u64* pref, co
 }
 
 // The direction policies of walk_groups.  res: the resolved requests (.depth); formula(): the request's
-// bits list candidate keys; seed(): the launch of
+// bits list candidate keys; sets(): the bit lists subject sets (Walk::smask); seed(): the launch of
 // level 0 -- true: *F is its frontier's size, false: read it back; level(): the launches of level j >=
 // FIRST_LEVEL on the frontier f -- *expanded == false: they built no next frontier, the group's walk ends.
 //
@@ -1407,6 +1467,7 @@ void launch_edges(Call& c, const Frontier& f, const Rows& r, const u64* pref, co
 struct ReverseWalk {
   const LReq* res;
   bool formula(uint32_t req) const { return res[req].mode == LK_FORMULA; }
+  bool sets(const GReq&) const { return false; }
   static constexpr int32_t FIRST_LEVEL = 1;
   bool seed(Call& c, const Walk& W, const GReq*, uint32_t gn, uint32_t*) const {
     hipLaunchKernelGGL(k_lk_seed, dim3(gn), dim3(256), 0, c.st, c.s->ds, W, (const LReq*)c.B.d_res.get());
@@ -1422,11 +1483,12 @@ struct ReverseWalk {
   }
 };
 
-// Forward: level j = 0 .. D-1 lists the subject ids of the frontier's check rows (emit) and, for the
-// requests that go one level further (xlive), follows its adj rows (expand).
+// Forward: level j = 0 .. D-1 lists the subject ids and subject sets of the frontier's check rows (emit) and,
+// for the requests that go one level further (xlive), follows its adj rows (expand).
 struct ForwardWalk {
   const SReq* res;
   bool formula(uint32_t req) const { return res[req].mode == LS_FORMULA; }
+  bool sets(const GReq& g) const { return g.sns != KG_SUBJECT_ID; }
   Rows check;  // the check rows
   static constexpr int32_t FIRST_LEVEL = 0;
   // the first frontier is the group's distinct roots: no readback before level 0
@@ -1442,7 +1504,7 @@ struct ForwardWalk {
     const RowLen<true> take{f, check.off, live, c.B.next.get(), nullptr};
     const RowLen<false> kept{f, ds.adj_off, xlive, nullptr, nullptr};
     if (int rc = prep_first(c, W, f.F, take, kept, scan_bytes)) return rc;
-    launch_edges(c, f, check, c.B.pref.get(), EmitIds{W});
+    launch_edges(c, f, check, c.B.pref.get(), Emit{ds, W});
     *expanded = xlive != 0;
     if (!xlive) return 0;
     const u64* apref = c.B.len.get();  // the prefix of the adj rows
@@ -1467,11 +1529,13 @@ int walk_groups(Call& c, const std::vector<GReq>& greq, const Dir& dir) {
     const uint32_t gn = (uint32_t)std::min<size_t>(64, greq.size() - g0);
     int32_t max_d = 1;
     for (uint32_t b = 0; b < gn; b++) max_d = std::max(max_d, dir.res[greq[g0 + b].req].depth);
-    u64 fmask = 0;
-    for (uint32_t b = 0; b < gn; b++)
+    u64 fmask = 0, smask = 0;
+    for (uint32_t b = 0; b < gn; b++) {
       if (dir.formula(greq[g0 + b].req)) fmask |= 1ull << b;
+      if (dir.sets(greq[g0 + b])) smask |= 1ull << b;
+    }
     Walk W{B.vis.get(), B.next.get(), B.fl[0].get(), 0, B.touched.get(), B.walk_nodes, B.okeys.get(), c.O.cap,
-           fmask, B.kkeys.get(), c.K.cap, B.greq.get() + g0, B.ctl.get(), c.pg != nullptr};
+           fmask, B.kkeys.get(), c.K.cap, B.greq.get() + g0, B.ctl.get(), c.pg != nullptr, smask};
     B.dirty = true;
     LkCtl h;
     uint32_t cur = 0, F = 0;
@@ -1694,21 +1758,32 @@ int unpaged_objects_tail(Call& c, u64 n_rows, kg_lookup_buf* out) {
 }
 
 // ------------------------------------------------------------------ host: the steps of a subject lookup
-// The plan: the walk's bits (walk mode: the root; formula mode: one per root of a walk leaf, *any_formula)
-// and the confirm-mode requests.
-void plan_subjects(Call& c, const kg_lookup_subj* reqs, const SReq* sr, std::vector<GReq>* greq, std::vector<uint32_t>* conf,
-                   bool* any_formula) {
+// The plan: the walk's bits (walk mode: the root; formula mode: one per root of a walk leaf, any_formula),
+// each with what its request lists, and the confirm-mode requests: those that list subject ids (conf) and
+// those that list subject sets, by filter sns << 32 | srel (by_filter).
+struct SubjPlan {
+  std::vector<GReq> greq;
+  std::vector<uint32_t> conf;
+  std::map<u64, std::vector<uint32_t>> by_filter;
+  bool any_formula = false;
+};
+void plan_subjects(Call& c, const kg_lookup_subj_set* reqs, const SReq* sr, SubjPlan* P) {
   const uint32_t nn = c.s->ds.n_nodes;
   for (size_t i = 0; i < c.n; i++) {
+    const kg_lookup_subj_set& x = reqs[i];
+    const bool ids = x.sns == KG_SUBJECT_ID;
     if (sr[i].mode == LS_WALK && sr[i].root < nn)
-      greq->push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].root, 0, {}});
+      P->greq.push_back(GReq{x.ns, x.rel, (uint32_t)i, sr[i].root, 0, {}, 0, x.sns, x.srel});
     else if (sr[i].mode == LS_FORMULA) {
       for (uint32_t t = 0; t < sr[i].n_froot && t < (uint32_t)FP_LEAVES; t++)
         if (sr[i].froot[t] < nn) {
-          greq->push_back(GReq{reqs[i].ns, reqs[i].rel, (uint32_t)i, sr[i].froot[t], 0, {}});
-          *any_formula = true;
+          P->greq.push_back(GReq{x.ns, x.rel, (uint32_t)i, sr[i].froot[t], 0, {}, 0, x.sns, x.srel});
+          P->any_formula = true;
         }
-    } else if (sr[i].mode == LS_CONFIRM) conf->push_back((uint32_t)i);
+    } else if (sr[i].mode == LS_CONFIRM) {
+      if (ids) P->conf.push_back((uint32_t)i);
+      else P->by_filter[((u64)x.sns << 32) | x.srel].push_back((uint32_t)i);
+    }
   }
 }
 
@@ -1746,8 +1821,60 @@ int subject_domain(Call& c, const uint32_t* csub, u64 n_rows, const uint32_t** d
   return 0;
 }
 
+// The candidates of the confirm requests that list subject sets: the per-filter domains out of the check rows
+// csub[0, n_rows) (k_ls_dom_sets), sorted; every distinct set of a filter becomes a candidate key request
+// << 32 | object id of that filter's requests (k_lk_domain) -- a paged call's at or above the request's cursor --
+// next to the formula requests' keys.  A step whose list was too small runs again.
+int set_candidates(Call& c, const std::map<u64, std::vector<uint32_t>>& by_filter, const uint32_t* csub, u64 n_rows) {
+  LookupBufs& B = c.B;
+  std::vector<uint32_t> blob;
+  const size_t at = tab_append(blob, by_filter, [](u64, const std::vector<uint32_t>&) { return false; });
+  blob.push_back(0);
+  HIPC(B.tab.reserve(blob.size() + 2));
+  HIPC(hipMemcpyAsync(B.tab.get(), blob.data(), blob.size() * 4, hipMemcpyHostToDevice, c.st));
+  HIPC(hipStreamSynchronize(c.st));  // blob is pageable
+  const GroupTab<u64> F = tab_on<u64>(B.tab.get(), at, by_filter.size());
+  CandTab T{};
+  T.ns = GroupTab<uint32_t>{nullptr, F.flag, F.off, F.req, F.n};  // k_lk_domain reads the slots' requests only
+  u64 dcap = std::max<u64>(65536, B.dkeys.cap()), nd = 0;
+  for (;;) {
+    HIPC(B.dkeys.reserve((size_t)dcap));
+    HIPC(hipMemsetAsync(&B.ctl.get()->dcount, 0, 8, c.st));
+    hipLaunchKernelGGL(k_ls_dom_sets, c.grid(n_rows), dim3(256), 0, c.st, c.s->ds, csub, n_rows, F, B.dkeys.get(), dcap,
+                       B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    if (h.dcount > dcap) {
+      dcap = h.dcount;
+      continue;
+    }
+    nd = h.dcount;
+    break;
+  }
+  if (!nd) return 0;
+  const u64* dk = nullptr;
+  if (int rc = sort_keys(c, B.dkeys, B.dkeys2, (size_t)nd, 64, &dk, (u64*)nullptr)) return rc;
+  for (;;) {
+    hipLaunchKernelGGL(k_lk_domain<true>, c.grid(nd), dim3(256), 0, c.st, T, dk, nd, (const kg_lookup*)nullptr,
+                       (kg_query*)nullptr, (uint32_t*)nullptr, (u64)0, B.kkeys.get(), c.K.cap,
+                       c.pg ? (const PgReq*)B.pst.get() : nullptr, B.ctl.get());
+    HIPC(hipGetLastError());
+    LkCtl h;
+    if (int rc = c.read_ctl(&h)) return rc;
+    if (h.kcount > c.K.cap) {
+      if (int rc = c.regrow(c.K, B.kkeys, h.kcount)) return rc;
+      if (int rc = c.rewind()) return rc;
+      continue;
+    }
+    c.K.have = h.kcount;
+    return 0;
+  }
+}
+
 // The end of an unpaged call: every (subject id of the domain, confirm request) pair, subject-id-major, then
-// the formula requests' candidate keys, one of each, through the check in chunks; the output.
+// the candidate keys (the formula requests', the subject sets of the confirm requests' filters), one of each,
+// through the check in chunks; the output.
 int unpaged_subjects_tail(Call& c, const std::vector<uint32_t>& conf, const uint32_t* dom, u64 n_dom, kg_lookup_buf* out) {
   LookupBufs& B = c.B;
   const ErrCount sink{B.n_errors.get(), B.errmin.get()};
@@ -1758,7 +1885,7 @@ int unpaged_subjects_tail(Call& c, const std::vector<uint32_t>& conf, const uint
     HIPC(hipStreamSynchronize(c.st));  // conf is pageable
     auto pair_rows = [&](u64 at, u64 m) -> int {
       hipLaunchKernelGGL(k_ls_cands, c.grid(m), dim3(256), 0, c.st, dom, n_dom, (const uint32_t*)B.tab.get(), C,
-                         (const kg_lookup_subj*)B.d_req.get(), at, m, B.cq.get(), B.creq.get());
+                         (const kg_lookup_subj_set*)B.d_req.get(), at, m, B.cq.get(), B.creq.get());
       return 0;
     };
     if (int rc = confirm<true>(c, n_dom * C, CHUNK_SUBJECTS, false, pair_rows, sink)) return rc;
@@ -1809,10 +1936,11 @@ static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const 
   return unpaged_objects_tail(c, n_rows, out);
 }
 
-// kg_lookup_subjects on lane L (as lookup_objects).  Walk-mode requests are listed by the forward walk,
-// 64 bits per group; formula-mode requests take a bit per walk-leaf root there, and what those list is
-// checked; the others by a check of every subject id of the domain.
-static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
+// kg_lookup_subject_sets on lane L (as lookup_objects; kg_lookup_subjects: every request lists ids).  Walk-mode
+// requests are listed by the forward walk, 64 bits per group; formula-mode requests take a bit per walk-leaf
+// root there, and what those list is checked; the others by a check of every subject id of the domain, or of
+// every subject set of their filter's domain.
+static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages, size_t n,
                               int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
   Call c(s, L, gmax);
   c.pg = pages;
@@ -1821,36 +1949,52 @@ static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, 
   const uint64_t n_rows = s->n_check_rows;
   const SReq* sr = nullptr;
   const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
-  if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj* d_req, SReq* d_sr) {
+  if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj_set* d_req, SReq* d_sr) {
         hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, c.st, ds, formula ? s->d_fidx : nullptr,
                            (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, d_sr);
       }))
     return rc;
-  std::vector<GReq> greq;
-  std::vector<uint32_t> conf;
-  bool any_formula = false;
-  plan_subjects(c, reqs, sr, &greq, &conf, &any_formula);
-  if (pages) {  // the confirm requests index the domain, the formula requests their unique keys
+  SubjPlan P;
+  plan_subjects(c, reqs, sr, &P);
+  if (pages) {  // the confirm requests for ids index the domain, the others their unique keys
     std::vector<uint8_t> implicit(n, 0);
-    for (uint32_t r : conf) implicit[r] = 1;
-    if (int rc = c.page_upload(greq, implicit)) return rc;
+    for (uint32_t r : P.conf) implicit[r] = 1;
+    if (int rc = c.page_upload(P.greq, implicit)) return rc;
   }
-  if (any_formula)
+  if (P.any_formula || !P.by_filter.empty())
     if (int rc = c.want_cand_keys()) return rc;
-  if (int rc = walk_groups(c, greq, ForwardWalk{sr, Rows{ds.crow_off ? ds.crow_off : ds.row_off, csub, n_rows}})) return rc;
+  if (int rc = walk_groups(c, P.greq, ForwardWalk{sr, Rows{ds.crow_off ? ds.crow_off : ds.row_off, csub, n_rows}}))
+    return rc;
   u64 n_dom = 0;
   const uint32_t* dom = nullptr;
-  if (!conf.empty() && n_rows && csub)
+  if (!P.conf.empty() && n_rows && csub)
     if (int rc = subject_domain(c, csub, n_rows, &dom, &n_dom)) return rc;
-  if (pages) return paged_tail<true>(c, dom, n_dom, !conf.empty(), pout);
-  return unpaged_subjects_tail(c, conf, dom, n_dom, out);
+  if (!P.by_filter.empty() && n_rows && csub)
+    if (int rc = set_candidates(c, P.by_filter, csub, n_rows)) return rc;
+  if (pages) return paged_tail<true>(c, dom, n_dom, !P.conf.empty(), pout);
+  return unpaged_subjects_tail(c, P.conf, dom, n_dom, out);
 }
 
 int lookup_objects(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
   return lookup_objects_on(s, L, reqs, nullptr, n, gmax, out, nullptr);
 }
+// kg_lookup_subjects' requests as requests that list ids
+static std::vector<kg_lookup_subj_set> id_requests(const kg_lookup_subj* reqs, size_t n) {
+  std::vector<kg_lookup_subj_set> v(n);
+  for (size_t i = 0; i < n; i++)
+    v[i] = kg_lookup_subj_set{reqs[i].ns, reqs[i].obj, reqs[i].rel, KG_SUBJECT_ID, 0, reqs[i].max_depth};
+  return v;
+}
 int lookup_subjects(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, size_t n, int32_t gmax, kg_lookup_buf* out) {
+  return lookup_subjects_on(s, L, id_requests(reqs, n).data(), nullptr, n, gmax, out, nullptr);
+}
+int lookup_subject_sets(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, size_t n, int32_t gmax,
+                        kg_lookup_buf* out) {
   return lookup_subjects_on(s, L, reqs, nullptr, n, gmax, out, nullptr);
+}
+int lookup_subject_sets_page(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages, size_t n,
+                             int32_t gmax, kg_lookup_pages* out) {
+  return lookup_subjects_on(s, L, reqs, pages, n, gmax, &out->list, out);
 }
 int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n, int32_t gmax,
                         kg_lookup_pages* out) {
@@ -1858,7 +2002,7 @@ int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lo
 }
 int lookup_subjects_page(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
                          int32_t gmax, kg_lookup_pages* out) {
-  return lookup_subjects_on(s, L, reqs, pages, n, gmax, &out->list, out);
+  return lookup_subjects_on(s, L, id_requests(reqs, n).data(), pages, n, gmax, &out->list, out);
 }
 
 void lookup_free(kg_lookup_buf* out) {

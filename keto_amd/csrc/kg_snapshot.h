@@ -491,6 +491,11 @@ int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lo
                         int32_t global_max_depth, kg_lookup_pages* out);
 int lookup_subjects_page(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
                          int32_t global_max_depth, kg_lookup_pages* out);
+// kg_lookup_subject_sets(_page): the subject lookup with a filter per request (subject ids, or the sets sns:*#srel)
+int lookup_subject_sets(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, size_t n, int32_t global_max_depth,
+                        kg_lookup_buf* out);
+int lookup_subject_sets_page(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages, size_t n,
+                             int32_t global_max_depth, kg_lookup_pages* out);
 void lookup_free(kg_lookup_buf* out);
 void lookup_bufs_free(void* bufs);
 // kg_query.hip: kg_snapshot_query on lane L (the caller holds L->w->mu); query_free returns its output

@@ -467,6 +467,57 @@ class Engine:
             raise CheckError(int(err[0]))
         return sorted(it.obj_name(int(i)) for i in ids)
 
+    # ---- subject-set lookup: the subject sets of one (namespace, relation) that hold a relation on an object
+    def lookup_subject_sets_ids(self, reqs: np.ndarray,
+                                with_stats: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """reqs: (n,6) uint32 kg_lookup_subj_set rows (ns, obj, rel, sns, srel, max_depth).  Returns (req_off u64
+        [n+1], ids u32 ascending per request, err_code u32 [n], n_errors u64 [n]): request i's ids are the
+        object ids o of the subject sets sns:o#srel that occur as a tuple's subject and whose check on the
+        request's object is IsMember -- with sns == KG_SUBJECT_ID, lookup_subjects_ids' subject ids.
+        last_stats as lookup_objects_ids."""
+        return self._lookup("kg_lookup_subject_sets", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6), with_stats)
+
+    def lookup_subject_sets_page_ids(self, reqs: np.ndarray, pages: np.ndarray, with_stats: bool = False):
+        """reqs as lookup_subject_sets_ids; pages and the result as lookup_objects_page_ids."""
+        return self._lookup_page("kg_lookup_subject_sets_page", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6),
+                                 pages, with_stats)
+
+    def _subject_set_row(self, namespace: str, object: str, relation: str, subject_namespace: str,
+                         subject_relation: str, rest_depth: int) -> Optional[np.ndarray]:
+        """The request row, or None where the filter names a namespace or relation the snapshot has never seen
+        (nothing is interned for it: no tuple's subject can match)."""
+        it = self.snapshot.interner
+        try:
+            sns, srel = it.ns_id(subject_namespace, create=False), it.rel_id(subject_relation, create=False)
+        except KeyError:
+            return None
+        return np.asarray([it.ns_id(namespace), it.obj_id(object), it.rel_id(relation), sns, srel,
+                           np.int32(rest_depth).view(np.uint32)], np.uint32)
+
+    def lookup_subject_sets(self, namespace: str, object: str, relation: str, subject_namespace: str,
+                            subject_relation: str, rest_depth: int) -> List[SubjectSet]:
+        """The subject sets subject_namespace:*#subject_relation that have `relation` on `namespace:object`,
+        directly or through nesting, sorted by object name.  Raises CheckError as lookup_subjects."""
+        row = self._subject_set_row(namespace, object, relation, subject_namespace, subject_relation, rest_depth)
+        if row is None:
+            return []
+        _, ids, err, nerr = self.lookup_subject_sets_ids(row)
+        if int(nerr[0]):
+            raise CheckError(int(err[0]))
+        it = self.snapshot.interner
+        return [SubjectSet(subject_namespace, o, subject_relation) for o in sorted(it.obj_name(int(i)) for i in ids)]
+
+    def lookup_subject_sets_page(self, namespace: str, object: str, relation: str, subject_namespace: str,
+                                 subject_relation: str, rest_depth: int, frm: int = 0,
+                                 limit: int = 100) -> Tuple[List[SubjectSet], Optional[int]]:
+        """One page of lookup_subject_sets in id order, as lookup_objects_page."""
+        row = self._subject_set_row(namespace, object, relation, subject_namespace, subject_relation, rest_depth)
+        if row is None:
+            return [], None
+        _, ids, err, nerr, nxt = self.lookup_subject_sets_page_ids(row, np.asarray([[frm, limit]], np.uint32))
+        names, nx = self._page_names(ids, err, nerr, nxt)
+        return [SubjectSet(subject_namespace, o, subject_relation) for o in names], nx
+
     # ---- paged lookups: the next `limit` ids from a cursor (kg_lookup_objects_page / kg_lookup_subjects_page)
     def lookup_objects_page_ids(self, reqs: np.ndarray, pages: np.ndarray, with_stats: bool = False):
         """reqs as lookup_objects_ids; pages: (n,2) uint32 (from, limit >= 1).  Returns (req_off, objs, err_code,

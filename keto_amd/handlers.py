@@ -355,26 +355,38 @@ class ListObjectsHandler:
 class ListSubjectsHandler:
     """Subject lookup over one engine (no reference counterpart; OpenFGA ListUsers' shape): the subject ids
     that have a relation on an object, in name order -- or id order with order=id -- paged like
-    ListObjectsHandler."""
+    ListObjectsHandler.  With a filter subject_set.namespace + subject_set.relation (OpenFGA's user filter
+    {type, relation}) the subject sets of that namespace and relation instead, paged the same way."""
 
     DEFAULT_PAGE_SIZE = ListObjectsHandler.DEFAULT_PAGE_SIZE
+    ERR_FILTER = 'a subject-set filter takes "subject_set.namespace" and "subject_set.relation", and no object'
 
     def __init__(self, engine: Engine, mapper: Mapper):
         self.engine, self.mapper = engine, mapper
 
     def _list(self, namespace: str, object: str, relation: str, max_depth: int, page_size: int,
-              page_token: str, order: str = "") -> dict:
+              page_token: str, order: str = "", sfilter: Optional[Tuple[str, str]] = None) -> dict:
         try:
             self.mapper.check_namespace(namespace)
         except NamespaceNotFound as e:
             raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+        if sfilter is None:
+            key, one = "subject_ids", (lambda name: name)
+            unpaged = lambda: self.engine.lookup_subjects(namespace, object, relation, max_depth)
+            paged = lambda frm, limit: self.engine.lookup_subjects_page(namespace, object, relation, max_depth, frm, limit)
+        else:
+            key = "subject_sets"
+            one = lambda s: {"namespace": s.namespace, "object": s.object, "relation": s.relation}
+            unpaged = lambda: self.engine.lookup_subject_sets(namespace, object, relation, sfilter[0], sfilter[1], max_depth)
+            paged = lambda frm, limit: self.engine.lookup_subject_sets_page(namespace, object, relation, sfilter[0],
+                                                                            sfilter[1], max_depth, frm, limit)
         by_id = parse_id_page(order, page_token, page_size)
         if by_id is not None:
             try:
-                names, nxt = self.engine.lookup_subjects_page(namespace, object, relation, max_depth, by_id[0], by_id[1])
+                names, nxt = paged(by_id[0], by_id[1])
             except CheckError as e:
                 raise HandlerError(500, str(e))
-            return {"subject_ids": names, "next_page_token": "" if nxt is None else str(nxt)}
+            return {key: [one(x) for x in names], "next_page_token": "" if nxt is None else str(nxt)}
         try:
             at = int(page_token) if page_token else 0
             if at < 0 or page_size < 1:
@@ -382,37 +394,50 @@ class ListSubjectsHandler:
         except ValueError:
             raise _bad("malformed page_token or page_size")
         try:
-            names = self.engine.lookup_subjects(namespace, object, relation, max_depth)
+            names = unpaged()
         except CheckError as e:
             raise HandlerError(500, str(e))
         page = names[at:at + page_size]
-        return {"subject_ids": page, "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
+        return {key: [one(x) for x in page], "next_page_token": str(at + page_size) if at + page_size < len(names) else ""}
+
+    def _filter(self, ns, obj, rel) -> Optional[Tuple[str, str]]:
+        """The subject-set filter of a request (each part None where it is not given), or None without one."""
+        if ns is None and obj is None and rel is None:
+            return None
+        if obj is not None or not ns or not rel:
+            raise _bad(self.ERR_FILTER)
+        return str(ns), str(rel)
 
     def get_list_subjects(self, query: Union[str, Query]) -> Tuple[int, dict]:
-        """GET ?namespace=&object=&relation=&max-depth=&page_size=&page_token=&order=."""
+        """GET ?namespace=&object=&relation=&max-depth=&page_size=&page_token=&order=
+        [&subject_set.namespace=&subject_set.relation=]."""
         try:
             q = parse_query(query)
             d = max_depth_from_query(q)
             if "namespace" not in q or "object" not in q or "relation" not in q:
                 raise _bad('incomplete request, provide "namespace", "object" and "relation"')
+            sfilter = self._filter(*(_get(q, k) if k in q else None
+                                     for k in (SUBJECT_SET_NS_KEY, SUBJECT_SET_OBJ_KEY, SUBJECT_SET_REL_KEY)))
             try:
                 size = parse_go_int(_get(q, "page_size")) if "page_size" in q else self.DEFAULT_PAGE_SIZE
             except ValueError:
                 raise _bad("malformed page_token or page_size")
             return 200, self._list(_get(q, "namespace"), _get(q, "object"), _get(q, "relation"), d, size,
-                                   _get(q, "page_token"), _get(q, "order"))
+                                   _get(q, "page_token"), _get(q, "order"), sfilter)
         except HandlerError as e:
             return e.status, e.body()
 
     def grpc_list_subjects(self, req: dict) -> dict:
-        """req = {"namespace", "object", "relation", "max_depth", "page_size", "page_token", "order"}.  Raises
-        HandlerError (grpc_code) on failure."""
+        """req = {"namespace", "object", "relation", "max_depth", "page_size", "page_token", "order"} and, to list
+        subject sets, "subject_set": {"namespace", "relation"}.  Raises HandlerError (grpc_code) on failure."""
         for k in ("namespace", "object", "relation"):
             if not req.get(k):
                 raise _bad('incomplete request, provide "namespace", "object" and "relation"')
+        f = req.get("subject_set")
+        sfilter = None if f is None else self._filter(f.get("namespace") or "", f.get("object"), f.get("relation") or "")
         return self._list(req["namespace"], req["object"], req["relation"], int(req.get("max_depth", 0)),
                           int(req.get("page_size", 0)) or self.DEFAULT_PAGE_SIZE, str(req.get("page_token", "")),
-                          str(req.get("order", "")))
+                          str(req.get("order", "")), sfilter)
 
 
 def relation_query_from_url_query(q: dict):

@@ -2,11 +2,17 @@
 and for a batch of 64, and for the same requests every object of the namespace through
 kg_check_batch_device (queries resident in HBM, so the brute force pays no host transfer).
 
-  python tools/lookup_bench.py [--mode objects|subjects] [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
+  python tools/lookup_bench.py [--mode objects|subjects|subject-sets] [--tuples 2000000] [--depth 10] [--reps 20] [--warmup 5]
                                [--preset 0|1] [--relation NAME] [--page N]
 
 --mode subjects measures the mirror image the same way: kg_lookup_subjects for one doc and for 64 docs
 against every subject id of the snapshot's tuples through kg_check_batch_device.
+
+--mode subject-sets measures kg_lookup_subject_sets for the same docs with the filter group#member ("which
+groups may do this on the doc?") against what a caller did before it: every subject set of the filter's domain
+(the group#member sets that occur as a tuple's subject) through kg_check_batch_device.  It prints both times,
+the domain size and `parity`, the number of requests whose two answers differ (it must be 0).  With --page N
+the paged call is timed beside the same brute force and the page compared with the brute force's first N.
 
 --preset 1 builds the C3 graph with its program (keto_amd/synth.py) and asks for --relation, by default
 the permission doc#share = view & !blocked: a boolean rewrite, which the lookups answer in formula mode
@@ -42,7 +48,7 @@ NS_DOC, REL_VIEWER, SUBJECT_ID = 0, 1, 0xFFFFFFFF  # the synthetic generator's i
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("objects", "subjects"), default="objects")
+    ap.add_argument("--mode", choices=("objects", "subjects", "subject-sets"), default="objects")
     ap.add_argument("--tuples", type=int, default=2_000_000)
     ap.add_argument("--depth", type=int, default=10)
     ap.add_argument("--reps", type=int, default=20)
@@ -93,6 +99,9 @@ def main(argv=None):
         out = {"gpu": out["gpu"], "preset": a.preset, "relation": relation, "tuples": out["tuples"], "nodes": out["nodes"],
                "domain_subject_ids": int(len(domain)),
                "depth": a.depth, "check_row_of_doc": int(rlen[mid[32]])}
+    if a.mode == "subject-sets":
+        print(json.dumps(subject_sets(a, eng, snap, L, keys, rows, relation, dev)))
+        return
     if a.page:
         out["page"] = a.page
         for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
@@ -156,6 +165,85 @@ def main(argv=None):
             out[name]["lookup_formula"] = by_key
         del q, dq, d_out, d_err
     print(json.dumps(out))
+
+
+def subject_sets(a, eng, snap, L, keys, rows, relation, dev):
+    """--mode subject-sets: the groups (group#member) that hold `relation` on one doc and on 64 docs, by the
+    lookup and by a check of every set of the filter's domain; --page: the first N of them by the paged call."""
+    import torch
+    from keto_amd import _lib
+    it = snap.interner
+    rel, sns, srel = it.rel_id(relation), it.ns_id("group"), it.rel_id("member")
+    domain = np.unique(rows[(rows[:, 3] == sns) & (rows[:, 5] == srel), 4])
+    # mid-reach docs: the 64 doc#viewer nodes around the median row length
+    viewer = rows[(rows[:, 0] == NS_DOC) & (rows[:, 2] == REL_VIEWER)]
+    docs, rlen = np.unique(viewer[:, 1], return_counts=True)
+    order = np.argsort(rlen, kind="stable")
+    mid = order[len(order) // 2 - 32:len(order) // 2 + 32]
+    reqs64 = np.zeros((64, 6), np.uint32)
+    reqs64[:, 0], reqs64[:, 1], reqs64[:, 2], reqs64[:, 3], reqs64[:, 4] = NS_DOC, docs[mid], rel, sns, srel
+    out = {"gpu": torch.cuda.get_device_name(0), "mode": "subject-sets", "preset": a.preset, "relation": relation,
+           "filter": "group#member", "tuples": int(len(rows)), "nodes": snap.info()["nodes"],
+           "domain_sets": int(len(domain)), "depth": a.depth, "row_of_doc": int(rlen[mid[32]])}
+    if a.page:
+        out["page"] = a.page
+    stream = torch.cuda.current_stream(dev)
+
+    def median_ms(fn):
+        xs = []
+        for k in range(a.warmup + a.reps):
+            t0 = time.perf_counter()
+            fn()
+            if k >= a.warmup:
+                xs.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(xs)
+
+    for name, reqs in (("one", reqs64[32:33]), ("batch64", reqs64)):
+        n = len(reqs)
+        q = torch.zeros((n, len(domain), 7), dtype=torch.int32, device=dev)  # kg_query rows, built in HBM
+        q[:, :, 0], q[:, :, 2], q[:, :, 3], q[:, :, 5] = NS_DOC, rel, sns, srel
+        q[:, :, 1] = torch.from_numpy(reqs[:, 1].copy().view(np.int32)).to(dev)[:, None]
+        q[:, :, 4] = torch.from_numpy(domain.view(np.int32)).to(dev)[None, :]
+        dq = q.reshape(-1, 7).contiguous()
+        d_out = torch.zeros(dq.shape[0], dtype=torch.uint8, device=dev)
+        d_err = torch.zeros(dq.shape[0], dtype=torch.int32, device=dev)
+        pages = np.stack([np.zeros(n, np.uint32), np.full(n, max(a.page, 1), np.uint32)], 1)
+
+        def brute():
+            _lib.check(L.kg_check_batch_device(snap.handle, dq.data_ptr(), dq.shape[0], a.depth, d_out.data_ptr(),
+                                               d_err.data_ptr(), None, C.c_void_p(stream.cuda_stream)), "check")
+            torch.cuda.synchronize()
+
+        def lookup():
+            if a.page:
+                return eng.lookup_subject_sets_page_ids(reqs, pages, with_stats=True)[:4]
+            return eng.lookup_subject_sets_ids(reqs, with_stats=True)
+
+        brute()
+        member = (d_out.cpu().numpy() == 1).reshape(n, len(domain))
+        entry = {"requests": n, "checks_brute": int(dq.shape[0])}
+        for key in reversed(keys):  # the default (None, or 1) last
+            if key is not None:
+                snap.tune("lookup_formula", key)
+            off, ids, err, nerr = lookup()
+            want = [domain[member[i]][:a.page] if a.page else domain[member[i]] for i in range(n)]
+            parity = sum(not np.array_equal(ids[int(off[i]):int(off[i + 1])], want[i]) for i in range(n)) + int(nerr.any())
+            ms = median_ms(lookup)
+            lookup()
+            st = eng.last_stats
+            e = {"lookup_ms": round(ms, 4), "lookup_kernel_ms": round(st["kernel_ms"], 4), "parity": int(parity),
+                 "n_objs": int(st["n_objs"]), "exact": int(st["exact"]), "candidates": int(st["candidates"]),
+                 "confirmed": int(st["confirmed"]), "levels": int(st["levels"])}
+            if a.page:
+                e["rounds"] = int(st["rounds"])
+            entry["lookup_formula=" + str(key)] = e
+        entry["brute_ms"] = round(median_ms(brute), 4)
+        entry["brute_over_lookup"] = round(entry["brute_ms"] / ms, 2)  # against the default mode
+        entry["parity"] = sum(v["parity"] for v in entry.values() if isinstance(v, dict))
+        out[name] = entry
+        del q, dq, d_out, d_err
+    out["parity"] = out["one"]["parity"] + out["batch64"]["parity"]
+    return out
 
 
 def page_entry(a, eng, snap, keys, reqs, have_paged):
