@@ -22,6 +22,11 @@
  * internal/persistence/sql/uuid_mapping.go:31-66 -- a dense id per UUID is equivalent):
  *   namespace ids  < 65535, relation ids < 65535 (global over namespaces),
  *   object ids     < 2^31-1, one space for objects AND subject ids (both are UUIDs upstream).
+ * Ids need not be dense.  A snapshot with a namespace program keeps tables of
+ * kg_dict.n_namespaces x kg_dict.n_relations entries, so it needs n_namespaces x n_relations <= 64 Mi
+ * (2^26); past that kg_snapshot_create returns KG_ERR_RESOURCE (-4).  Without a program no such table
+ * is built and both may reach 65535.  A subject id costs one bit of a bitmap of (largest held subject
+ * id + 1) bits: 256 MiB when subject ids reach 2^31-2.
  * Rows must be passed in shard_id order (the order GetRelationTuples returns them).
  */
 #ifndef KETOGPU_H
@@ -66,7 +71,8 @@ static inline int kg_pack_query(const kg_query* q, kg_query_packed* p) {
   const uint32_t sns = q->t.sns == 0xFFFFFFFFu ? KG_PACK_SUBJECT_ID : q->t.sns;
   const uint32_t srel = q->t.sns == 0xFFFFFFFFu ? 0u : q->t.srel;
   const uint32_t d = q->max_depth <= 0 ? 0u : (q->max_depth > 65535 ? 65535u : (uint32_t)q->max_depth);
-  if (q->t.ns > KG_PACK_ID_MAX || q->t.rel > KG_PACK_ID_MAX || (sns != KG_PACK_SUBJECT_ID && sns > KG_PACK_ID_MAX) ||
+  /* a subject-set namespace of 4095 does not fit either: it would read back as the subject-id marker */
+  if (q->t.ns > KG_PACK_ID_MAX || q->t.rel > KG_PACK_ID_MAX || (q->t.sns != 0xFFFFFFFFu && sns > KG_PACK_ID_MAX) ||
       srel > KG_PACK_ID_MAX)
     return -2;
   p->obj = q->t.obj;
@@ -76,7 +82,8 @@ static inline int kg_pack_query(const kg_query* q, kg_query_packed* p) {
   return 0;
 }
 
-/* An expand root: a subject set, or a subject id (sns = KG_SUBJECT_ID) -- BuildTree's Subject. */
+/* An expand root: a subject set, or a subject id (sns = KG_SUBJECT_ID) -- BuildTree's Subject.  A subject-id
+ * root is one Leaf record naming the id; an id outside the id space (>= 2^31-1) is named as 2^31-1. */
 typedef struct {
   uint32_t sns, sobj, srel;
   int32_t max_depth;
@@ -137,8 +144,8 @@ typedef struct {
   uint64_t light_wave_max_ticks;        /* k_stream4: longest wave lifetime              */
   /* the tail tier's level kernels (round 6): the grid tier's k_grid_level or the MS-BFS k_ms_level */
   double tail_ms;                       /* summed device time of those launches (HIP events per launch; only with kg_snapshot_tune "level_events" 1) */
-  uint64_t tail_launches;               /* level launches of the batch (the first 64 are timed)          */
-  uint64_t tail_kind;                   /* 0 none, 1 k_grid_level, 2 k_ms_level                          */
+  uint64_t tail_launches;               /* level launches of the batch (the first 64 are timed); "level_events" 1 only */
+  uint64_t tail_kind;                   /* 0 none, 1 k_grid_level, 2 k_ms_level; "level_events" 1 only    */
   uint64_t tail_rows, tail_edges, tail_probes, tail_logged; /* the tail tier's share of the counters    */
   uint64_t ms_edges_loaded;             /* k_ms_level: adjx records loaded (an edge with work in any word) */
   uint64_t ms_words_active;             /* k_ms_level: (edge, 64-query word) pairs with work              */
@@ -238,56 +245,51 @@ int kg_snapshot_info(const kg_snapshot* s, uint64_t* info4);
  * itself), [2] check-row entries (the direct tuples the union nodes hold).  KG_MATERIALIZE=0 in
  * the environment at snapshot creation turns it off. */
 int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
-/* Engine knobs (no reference counterpart; tuning and tests).  Results never depend on any of them.
- * key "back": 1 = the backward tier (reverse search from the subject's holders, one wave per query,
- * then one workgroup per query) takes the stream tier's overflow before the grid tier, and k_resolve
- * answers queries whose subject no row holds; 2 = the same with the wave width only (its overflow
- * goes straight to the grid tier; default); 0 = off.
- * key "stream_ecap": edges a query may enqueue in the stream tier before it is handed to the
- * backward / grid tiers (default 512; 0 = no budget) -- cuts the stream kernel's tail of long walks.
- * key "resolve_unheld" (0..2): without a namespace program, k_resolve reads a subject id's holder
- * bit before the node map and answers an unheld subject NotMember without the lookup (default 1);
- * 2 = the bit is read only by queries that the node map and the root probe leave for the stream
- * tier; 0 = the bit beside the node-map lookup for every query.
- * key "device_sync" (0/1): the same for kg_check_batch_device when it waits (stats or a grid-tier
- * readback; default 1: asleep -- 5.6 -> 5.8 x 10^9 checks/s with 4 batches in flight).  key "host_sync" (0/1): kg_check_batch waits for its device work asleep on a blocking-sync event
- * (1, default: no core spins per in-flight batch) or spinning in hipStreamSynchronize (0).
- * key "stream_steal" (1..8): XCD ranges of the work list a k_stream4 wave dequeues from (default 4:
- * when the list drains every wave walks them, one atomic each on a few hot words).
- * key "stream_chunk" (1..64): queries a k_stream4 wave dequeues at once (default 64).
- * key "stream_wgs": k_stream4 workgroups per CU (0 = 2; default 2); "back_wgs" (1..3, default 3), "back_edges" (reverse edges one backward-tier query may read, 0 = 2^12)
- * and "grid_wgs" (1..64, default 2): k_back / k_grid_level workgroups per CU (defaults = bench.py's C2 set).  key "shard_vis": log2 of the
- * hash-sharded mode's per-batch (query, node) visited table (default 25).  key "interp_cap2"
- * (0..4194304): BFS list cap of the rewrite interpreter's many-slot HBM pass (0 = 256 Ki nodes);
- * queries that outgrow it rerun in the single full-size slot.  key "interp_wgs" (1..8): workgroups
- * of 4 query waves per CU in the interpreter's LDS pass (default 6).  key "grid_reserve": allocate
- * now the grid tier's shared full-size pool (used by a query that overflows a workspace's pool on
- * its own; otherwise allocated on first need).  key "grid_cap": log entries of a workspace's grid
- * pool (0 = 16 Mi; small values force the overflow paths in tests).  key "max_lanes" (1..1024, default
- * 32): lane sets (a stream, staging and workspace per replica) that concurrent kg_check_batch /
- * kg_expand_batch calls check out of the snapshot's pool; at the cap a call waits for one to return.
+/* Engine knobs (no reference counterpart; tuning and tests).  Results never depend on any of them.  An
+ * unknown key, or a value outside the key's range, returns -2.
+ * Check tiers.  key "stream_ecap" (0..2^32-1, default 512; 0 = no budget): edges a query may enqueue in
+ * the stream tier before it is handed to the backward / grid tiers -- cuts the stream kernel's tail of
+ * long walks.  key "stream_steal" (1..8, default 4): XCD ranges of the work list a k_stream4 wave
+ * dequeues from (when the list drains every wave walks them, one atomic each on a few hot words).
+ * key "stream_wgs" (0..8, default 2; 0 = 2): k_stream4 workgroups per CU.  key "back_wgs" (1..3,
+ * default 3) and "grid_wgs" (1..64, default 2): k_back / k_grid_level workgroups per CU.  key
+ * "back_edges" (0..2^20, default 0 = 2^12): reverse edges one backward-tier query may read before it
+ * goes on to the grid tier.  key "interp_cap2" (0..4194304, default 0 = 256 Ki nodes): BFS list cap
+ * of the rewrite interpreter's many-slot HBM pass; queries that outgrow it rerun in the single
+ * full-size slot.  key "grid_reserve" (any value): allocate now the grid tier's shared full-size pool
+ * (used by a query that overflows a workspace's pool on its own; otherwise allocated on first need).
+ * key "grid_cap" (0..2^34, default 0 = 16 Mi): log entries of a workspace's grid pool (small values
+ * force the overflow paths in tests).  key "max_lanes" (1..1024, default 32): lane sets (a stream,
+ * staging and workspace per replica) that concurrent kg_check_batch / kg_expand_batch calls check out
+ * of the snapshot's pool; at the cap a call waits for one to return.
  * key "grid_ms" (0/1, default 1): the grid tier's queries run as a multi-source bit-parallel BFS,
- * 64 x "grid_ms_words" (1..16, default 8) queries per group sharing each level's walk, when one
- * group's dense per-node masks (32 B per word per node) fit an eighth of "grid_ms_bytes" (default
- * 2^30 per in-flight batch; the width halves until they do) -- graphs of up to ~4 M nodes.  key
- * "grid_ms_tg_cap" (default 256): a query whose subject has more holders is probed in dset per
- * newly reached node instead of marking its holders in the group's target masks.  key "grid_ms_cap": entries per MS-BFS level buffer (0 = 16 Mi; small values force the
- * overflow reruns in tests).
- * key "grid_bidir" (0..2^31-1, default 0): grid-tier slots whose subject has at most this many
- * holders alternate forward and backward turns (0: forward only).  key "expand_gw" (0/1, default 1): roots
- * that outgrow the LDS passes gather their neighbourhood in parallel and walk the copy (small and large
- * workgroup slots, then the hash pass); "expand_skip_lds" (0/1/2, tests): 1 = every root skips the LDS
- * passes, 2 = the 16-lane walkers are skipped and the 64-lane LDS pass takes every root;
- * "expand_hash_cap" (4..2^18, default 2^18, tests): visited sets per hash-pass slot (small values send
- * roots on to the whole-graph bitmap pass).
- * Hash-sharded mode: key "shard_wgs"
- * (1..64, default 8) k_shard_level workgroups per CU; "shard_heavy" (default 64) set rows longer than
- * this go to k_shard_heavy, which spreads their edges over the grid (0: every row); "shard_vis_mode"
- * 0 = exact (query, node) CAS table (default), 1 = lossy direct-mapped cache; "shard_pack" (0/1,
- * default 0): kg_shard_levels sends a locally owned child as its set-row begin and length (no
- * adj_off read at the next level; no namespace program, depths < 256); "shard_budget" /
- * "shard_back_budget": see kg_shard_back_* below; "shard_bucket" (0..2^26, default 0 = sized from the
- * batch): the first bucket size (records per destination) of in-library bindings made after it. */
+ * 64 x "grid_ms_words" (1, 2, 4, 8 or 16; default 8) queries per group sharing each level's walk, when
+ * one group's dense per-node masks (32 B per word per node) fit an eighth of "grid_ms_bytes"
+ * (2^20..2^40, default 2^30 per in-flight batch; the width halves until they do) -- graphs of up to
+ * ~4 M nodes -- and the batch's global depth is at most 32 (one depth mask per hop; deeper batches take
+ * the per-query rounds).  key "grid_ms_tg_cap" (0..2^31-1, default 256): a query whose subject has
+ * more holders is probed in dset per newly reached node instead of marking its holders in the group's
+ * target masks.  key "grid_ms_cap" (0..2^28, default 0 = 16 Mi): entries per MS-BFS level buffer
+ * (small values force the overflow reruns in tests).  key "level_events" (0/1, default 0): time every
+ * tail launch with HIP events (kg_stats.tail_ms).
+ * Expand.  key "expand_gw" (0/1, default 1): roots that outgrow the LDS passes gather their
+ * neighbourhood in parallel and walk the copy (small and large workgroup slots, then the hash pass);
+ * "expand_gw_wait_us" (0..10^7, default 100000): how long such a root waits for a free slot;
+ * "expand_skip_lds" (0/1/2, default 0; tests): 1 = every root skips the LDS passes, 2 = the 16-lane
+ * walkers are skipped and the 64-lane LDS pass takes every root; "expand_hash_cap" (4..2^18, default
+ * 2^18; tests): visited sets per hash-pass slot (small values send roots on to the whole-graph bitmap
+ * pass).
+ * Lookups and listing.  "lookup_cap", "lookup_domain_rows", "lookup_formula" and "query_cap" are
+ * described with kg_lookup_objects and kg_snapshot_query below (defaults 0, 0, 1, 0).
+ * Hash-sharded mode.  key "shard_vis" (10..34, default 23): log2 of the per-batch (query, node) visited
+ * table.  "shard_heavy" (0..2^32-1, default 64): set rows longer than this go to k_shard_heavy, which
+ * spreads their edges over the grid (0: every row).  "shard_budget" (default 0 = off) /
+ * "shard_back_budget" (default 2^14): see kg_shard_back_* below.  "shard_bucket" (0..2^26, default 0 =
+ * sized from the batch): the first bucket size (records per destination) of in-library bindings made
+ * after it.  "shard_local" (0/1, default 1), "shard_force_exchange" (0/1, default 0), "shard_remote_meta"
+ * (0/1, default 1), "shard_max_reruns" (0..64, default 0 = max(4, exchanges)) and "shard_max_bytes"
+ * (>= 0, default 0 = a quarter of the free HBM): see the hash-sharded calls below.
+ * "shard_force_overflow" (0/1, default 0; tests): every exchange run counts as overflowed, so the rerun paths run. */
 int kg_snapshot_tune(kg_snapshot* s, const char* key, int64_t value);
 /* Synthetic layout: ids6 = {n_docs, n_groups, n_users, n_folders, user_obj0, folder_obj0}
  * (doc d = object d, group g = object n_docs+g, user u = object user_obj0+u). */

@@ -1249,8 +1249,8 @@ __global__ __launch_bounds__(256) void k_pack(const kg_query* __restrict__ q, ui
   const uint32_t sns = x.t.sns == KG_SUBJECT_ID ? KG_PACK_SUBJECT_ID : x.t.sns;
   const uint32_t srel = x.t.sns == KG_SUBJECT_ID ? 0u : x.t.srel;
   const uint32_t d = x.max_depth <= 0 ? 0u : (x.max_depth > 65535 ? 65535u : (uint32_t)x.max_depth);
-  if (x.t.ns > KG_PACK_ID_MAX || x.t.rel > KG_PACK_ID_MAX || (sns != KG_PACK_SUBJECT_ID && sns > KG_PACK_ID_MAX) ||
-      srel > KG_PACK_ID_MAX)
+  if (x.t.ns > KG_PACK_ID_MAX || x.t.rel > KG_PACK_ID_MAX || (x.t.sns != KG_SUBJECT_ID && sns > KG_PACK_ID_MAX) ||
+      srel > KG_PACK_ID_MAX)  // a set namespace of 4095 would read back as the subject-id marker
     atomicOr(bad, 1u);
   pk[i] = make_uint4(x.t.obj, x.t.sobj, x.t.ns | (x.t.rel << 12) | ((sns & 0xFFu) << 24),
                      (sns >> 8) | (srel << 4) | (d << 16));

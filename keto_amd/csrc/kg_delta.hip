@@ -460,7 +460,7 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
   h_row_off_last = total;
   n_set_edges = n_adj;
   // 6. everything derived, as in a full build
-  if (upload_program(dict, prog)) return -1;
+  if (int rc = upload_program(dict, prog)) return rc;  // -1, or the resource error of a table past its limit
   if (has_program && device_flags()) return -1;
   n_check_rows = h_row_off_last;
   if (augment_rewrites() || build_formulas()) return -1;

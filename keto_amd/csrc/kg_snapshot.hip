@@ -831,7 +831,7 @@ int Snapshot::create_from_tuples(const kg_tuple* rows, size_t n, const kg_dict* 
   }
   h_row_off_last = h_row_off[nn];
   // 3. program + purity closure
-  if (upload_program(dict, prog)) return -1;
+  if (int rc = upload_program(dict, prog)) return rc;  // -1, or the resource error of a table past its limit
   std::vector<uint8_t> flags;
   if (has_program) {
     flags.assign(nn, 0);
@@ -961,7 +961,7 @@ int Snapshot::create_synthetic(const kg_synth_params* p, const kg_rewrite_prog* 
   h_row_off_last = tot[0];
   n_set_edges = tot[1];
   kg_dict dict{4, 10, 0};
-  if (upload_program(&dict, prog)) return -1;
+  if (int rc = upload_program(&dict, prog)) return rc;
   if (has_program && device_flags()) return -1;
   n_check_rows = h_row_off_last;
   if (augment_rewrites() || build_formulas()) return -1;

@@ -444,7 +444,8 @@ static int clamp_depth(int rest, int global) {
 }
 
 static uint32_t subject_tag(const ko_index* ix, const ko_tuple* q) {
-  if (q->sns == KO_SUBJECT_ID) return q->sobj & ~SET_BIT;
+  /* subject ids are < 2^31-1 (ketogpu.h): an id past that is one no tuple can hold, not an alias of id & 0x7FFFFFFF */
+  if (q->sns == KO_SUBJECT_ID) return q->sobj < 0x7FFFFFFFu ? q->sobj : NONE;
   uint32_t sn = node_find(ix, q->sns, q->sobj, q->srel);
   return sn == NONE ? NONE : (SET_BIT | sn);
 }
@@ -583,7 +584,7 @@ int64_t ko_expand(const ko_index* ix, uint32_t sns, uint32_t sobj, uint32_t srel
   if (!ix->finalized) return -1;
   tbuf t = {buf, cap_records * 6, 0, 0};
   uint32_t subj;
-  if (sns == KO_SUBJECT_ID) subj = sobj & ~SET_BIT;
+  if (sns == KO_SUBJECT_ID) subj = sobj < 0x7FFFFFFFu ? sobj : 0x7FFFFFFFu; /* out of range: the leaf names 2^31-1 */
   else {
     uint32_t v = node_find(ix, sns, sobj, srel);
     if (v == NONE) return 0; /* no rows anywhere: BuildTree returns nil */

@@ -125,6 +125,10 @@ class Oracle:
 
     def check_batch(self, q: np.ndarray, depths: np.ndarray, global_max: int, policy: int = POLICY_CANONICAL,
                     nthreads: int = 1):
+        """Depth cap: the canonical policy recurses once per depth level around a cycle, on the C stack of the
+        calling or worker thread -- a 40-cycle answers at depth 32,768 and overflows the stack at 65,535.  Keep
+        queries whose walk can enter a cycle at a depth of at most 4,096 (tests/test_gpu_depth_limits.py does);
+        a walk that meets no cycle recurses only as deep as it is long, whatever the depth."""
         q = np.ascontiguousarray(q, dtype=np.uint32).reshape(-1, 6)
         d = np.ascontiguousarray(depths, dtype=np.int32)
         out = np.zeros(q.shape[0], np.uint8)
