@@ -135,7 +135,7 @@ typedef struct {
   uint64_t n_wide;                      /* reserved (0) */
   uint64_t n_grid;                      /* queries resolved by the grid tier             */
   uint64_t n_back;                      /* queries resolved by the backward tier         */
-  uint64_t n_no_holder;                 /* queries answered NotMember by k_resolve: no row holds the subject */
+  uint64_t n_no_holder;                 /* queries answered NotMember by k_resolve: no row holds the subject, or its holder signature rules the root out */
   uint64_t back_rows, back_edges;       /* backward tier: parent lists opened / parents read */
   uint64_t light_steps;                 /* k_stream4: wave steps (one HBM round trip each) */
   uint64_t light_waves;                 /* k_stream4: waves that ran                     */
@@ -271,7 +271,8 @@ int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
  * more holders is probed in dset per newly reached node instead of marking its holders in the group's
  * target masks.  key "grid_ms_cap" (0..2^28, default 0 = 16 Mi): entries per MS-BFS level buffer
  * (small values force the overflow reruns in tests).  key "level_events" (0/1, default 0): time every
- * tail launch with HIP events (kg_stats.tail_ms).
+ * tail launch with HIP events (kg_stats.tail_ms).  key "holder_sig" (0/1, default 1; tests, A/B): 0 = k_resolve
+ * ignores the holder signatures (kg_snapshot_holder_sig) and rules out only subjects that no row holds.
  * Expand.  key "expand_gw" (0/1, default 1): roots that outgrow the LDS passes gather their
  * neighbourhood in parallel and walk the copy (small and large workgroup slots, then the hash pass);
  * "expand_gw_wait_us" (0..10^7, default 100000): how long such a root waits for a free slot;
@@ -291,6 +292,13 @@ int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
  * (>= 0, default 0 = a quarter of the free HBM): see the hash-sharded calls below.
  * "shard_force_overflow" (0/1, default 0; tests): every exchange run counts as overflowed, so the rerun paths run. */
 int kg_snapshot_tune(kg_snapshot* s, const char* key, int64_t value);
+/* Holder signatures (no reference counterpart): per subject id, 8 or 16 hash bits naming the nodes that hold
+ * it in a row or lie above such a node through subject sets; a check whose root's bit is missing is NotMember at
+ * every depth and is answered without a walk (counted in kg_stats.n_no_holder).  Built with the snapshot, and
+ * again from its own rows by kg_snapshot_apply, for one-rank snapshots without a namespace program;
+ * KG_HSIG_BITS in the environment at build picks the width (0 = none, 8, 16 = default).  Returns the width of
+ * replica 0's table, 0 when the snapshot has none. */
+int kg_snapshot_holder_sig(const kg_snapshot* s);
 /* Synthetic layout: ids6 = {n_docs, n_groups, n_users, n_folders, user_obj0, folder_obj0}
  * (doc d = object d, group g = object n_docs+g, user u = object user_obj0+u). */
 int kg_synth_ids(const kg_snapshot* s, uint32_t* ids6);

@@ -154,7 +154,7 @@ class kg_synth_params(C.Structure):
 # every symbol include/ketogpu.h declares
 EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic", "kg_snapshot_synthetic_on",
            "kg_snapshot_replicas", "kg_snapshot_destroy", "kg_snapshot_info", "kg_snapshot_materialized", "kg_snapshot_tune", "kg_synth_ids",
-           "kg_snapshot_create_ordered", "kg_snapshot_apply",
+           "kg_snapshot_holder_sig", "kg_snapshot_create_ordered", "kg_snapshot_apply",
            "kg_snapshot_export", "kg_snapshot_rows", "kg_snapshot_export_csr", "kg_check_batch", "kg_check_batch_device", "kg_check_batch_packed_device", "kg_pack_queries_device", "kg_synth_queries",
            "kg_expand_batch", "kg_expand_batch_device", "kg_tree_free", "kg_last_error", "kg_version", "kg_check_batch_packed", "kg_shard_owner", "kg_snapshot_create_shard",
            "kg_snapshot_synthetic_shard", "kg_shard_seed", "kg_shard_level", "kg_shard_level_seg", "kg_shard_finish",
@@ -258,6 +258,9 @@ def load(path: str = LIB_PATH):
         L.kg_lookup_subject_sets.restype = C.c_int
         L.kg_lookup_subject_sets_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
         L.kg_lookup_subject_sets_page.restype = C.c_int
+    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_snapshot_holder_sig"):
+        L.kg_snapshot_holder_sig.argtypes = [vp]
+        L.kg_snapshot_holder_sig.restype = C.c_int
     L.kg_snapshot_query.argtypes = [vp, vp, sz, C.POINTER(kg_query_buf)]
     L.kg_snapshot_query.restype = C.c_int
     L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]

@@ -471,6 +471,11 @@ static int tune_one(Snapshot* s, const char* key, int64_t value) {
     return 0;
   }
 
+  if (strcmp(key, "holder_sig") == 0) {
+    if (value < 0 || value > 1) return set_error(-2, "holder_sig must be 0 or 1");
+    s->holder_sig = (int)value;
+    return 0;
+  }
   if (strcmp(key, "stream_steal") == 0) {
     if (value < 1 || value > 8) return set_error(-2, "stream_steal must be in [1, 8]");
     s->stream_steal = (uint32_t)value;
@@ -597,6 +602,12 @@ int kg_snapshot_tune(kg_snapshot* sp, const char* key, int64_t value) {
   for (size_t i = 0; i < s->n_replicas(); i++)
     if (int rc = tune_one(s->replica(i), key, value)) return rc;
   return 0;
+}
+
+int kg_snapshot_holder_sig(const kg_snapshot* sp) {
+  if (!sp) return set_error(-2, "NULL snapshot");
+  const Snapshot* s = reinterpret_cast<const Snapshot*>(sp);
+  return s->ds.hsig ? (int)s->ds.hsig_w : 0;
 }
 
 int kg_synth_ids(const kg_snapshot* sp, uint32_t* ids6) {

@@ -184,18 +184,28 @@ __global__ __launch_bounds__(256) void k_resolve(DevSnap s, const kg_query* __re
     const bool sid = x.t.sns == KG_SUBJECT_ID;
     uint32_t subj = sid ? (x.t.sobj < 0x7FFFFFFFu ? x.t.sobj : NONE) : NONE;
     const bool want_h = no_holder_filter && sid && subj != NONE;
-    // no-holder test for a subject id: one bit of the holder bitmap (36 MB at 1 B tuples, stays in
-    // the Infinity Cache) instead of a random line of the holder hash
+    // no-holder test for a subject id: one entry of the holder signatures (2 B per subject id: the user
+    // range, ~200 MB at 1 B tuples, mostly stays in the Infinity Cache), or one bit of the holder bitmap where the
+    // snapshot has no signatures -- instead of a random line of the holder hash.  hw != 0 <=> some row holds subj
     const bool use_bits = want_h && s.hbits != nullptr;
+    const bool use_sig = use_bits && s.hsig != nullptr;
     const uint64_t hi = mix64(subj) & s.hmask;
     HSlot h0{};
     uint32_t hw = 0;
-    if (use_bits) hw = subj < s.hbits_n ? ld_once(s.hbits + (subj >> 5)) : 0u;
-    else if (want_h && !use_bits) h0 = s.hslots[hi];
+    if (use_sig) {
+      if (subj < s.hbits_n)
+        hw = s.hsig_w == 16 ? (uint32_t)ld_once(reinterpret_cast<const uint16_t*>(s.hsig) + subj) : (uint32_t)ld_once(s.hsig + subj);
+    } else if (use_bits) {
+      hw = subj < s.hbits_n ? (ld_once(s.hbits + (subj >> 5)) >> (subj & 31)) & 1u : 0u;
+    } else if (want_h) {
+      h0 = s.hslots[hi];
+    }
     // without a namespace program nothing can end as an error, so a subject that no row holds is
-    // NotMember whatever the root: the bit (an Infinity-Cache hit) is read first and such a query
-    // never touches the node map (~13 % of the C2 batch; one random HBM line each)
-    const bool unheld = no_holder_filter == 2 && use_bits && !s.relflags && !((hw >> (subj & 31)) & 1u);
+    // NotMember whatever the root: the entry (an Infinity-Cache hit) is read first and such a query
+    // never touches the node map (~13 % of the C2 batch; one random HBM line each).  The same goes for a
+    // held subject whose signature lacks the root's bit: the root is neither a holder of subj nor above
+    // one through set-adjacency, so no depth reaches subj from it (most of the other negatives)
+    const bool unheld = no_holder_filter == 2 && use_bits && !s.relflags && !(hw & (use_sig ? hsig_bit(key, s.hsig_w) : 1u));
     NSlot n0{};
     if (key_ok && !unheld) n0 = ld_once(s.nmap + ni);
     uint32_t node = NONE, rb = 0, rl = 0, rsig_lo = 0xFFFFFFFFu, rsig = 0xFFFFFFFFu, nfl = 0, icnt = 0;
@@ -247,7 +257,7 @@ __global__ __launch_bounds__(256) void k_resolve(DevSnap s, const kg_query* __re
       // depth that cannot reach any child (D < 2) finishes the query before the wave tier.  The
       // row signature in the node-map slot rules out most misses without touching dset.
       // an unset holder bit rules the probe out as well (the exact tuple would make subj a holder)
-      const bool nobit = use_bits && !((hw >> (subj & 31)) & 1u);
+      const bool nobit = use_bits && hw == 0;
       if (icnt) {
         // the whole check row is in the slot: exact, no dset line
         member = subj != NONE && nslot_inline_has(icnt, rpad, rsig, subj);
@@ -258,7 +268,7 @@ __global__ __launch_bounds__(256) void k_resolve(DevSnap s, const kg_query* __re
       if (member || d < 2 || rl == 0) route = ROUTE_DONE;
       // a subject that no row holds cannot be reached from any root (checkDirect never hits)
       if (route == ROUTE_LIGHT && no_holder_filter) {
-        const uint32_t cnt = use_bits ? ((hw >> (subj & 31)) & 1u)
+        const uint32_t cnt = use_bits ? hw
                              : want_h ? (h0.key == subj ? h0.count
                                                         : (h0.key == NONE ? 0u : holders_find(s, subj).y))
                                       : holders_find(s, subj).y;
@@ -1051,7 +1061,10 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
   if (n) {
     const bool use_back = s->ds.radj != nullptr;
     const uint32_t nblk = (uint32_t)((n + 255) / 256);
-    hipLaunchKernelGGL(k_resolve, dim3(nblk), dim3(256), 0, stream, s->ds, d_q, pq, (uint32_t)n, (uint32_t)n_base, n_extra,
+    // kg_snapshot_tune "holder_sig" 0: k_resolve does not see the signatures and reads the holder bitmap
+    DevSnap rs = s->ds;
+    if (!s->holder_sig) rs.hsig = nullptr;
+    hipLaunchKernelGGL(k_resolve, dim3(nblk), dim3(256), 0, stream, rs, d_q, pq, (uint32_t)n, (uint32_t)n_base, n_extra,
                        global_max_depth, rq, d_out, d_err, gen, use_back ? 2 : 0, ctl, lq,
                        lq_cap);
     HIPC(hipGetLastError());

@@ -19,8 +19,13 @@
 //                                        through set-adjacency (needs the rewrite interpreter).
 //   radj_off[n_nodes+1] u64 / radj[] u32  reverse set-adjacency (parents), for the backward tier.
 //   hold[] u32 + subject hash             holders: the nodes whose row contains a given subject,
-//   hbits[] u32                           holder bitmap over subject ids (k_resolve's no-holder test)
 //                                        grouped by subject (the backward tier's level 0).
+//   hbits[] u32                           holder bitmap over subject ids: bit s set <=> some row holds s
+//                                        (lookups, the hash-sharded seed; k_resolve without hsig).
+//   hsig[] u8 / u16                       holder signature per subject id (k_resolve's no-holder test): the
+//                                        hsig_bit of every node that holds s or lies above a holder through
+//                                        radj; 0 <=> no row holds s.  One-rank snapshots without a namespace
+//                                        program only (nullptr otherwise).
 //   nlive[n_nodes] u8                     refreshed snapshots only: the node still occurs in a tuple
 //                                        (kg_lookup_objects' domain); nullptr: every node does.
 #pragma once
@@ -74,6 +79,12 @@ __host__ __device__ __forceinline__ uint64_t hash_next(uint64_t i, uint64_t n) {
 __host__ __device__ __forceinline__ uint64_t dset_home(uint64_t key, uint64_t n) {
   const uint64_t x = key * 0x9E3779B97F4A7C15ull;
   return ((x >> 32) * n + (((x & 0xFFFFFFFFull) * n) >> 32)) >> 32;
+}
+
+// Bit of a node (by its node-map key) in the holder signatures (DevSnap::hsig, `width` = 8 or 16 bits):
+// the low bits of the key's mix64 -- the node map's home slot comes from the high ones.
+__host__ __device__ __forceinline__ uint32_t hsig_bit(uint64_t key, uint32_t width) {
+  return 1u << (uint32_t)(mix64(key) & (width - 1));
 }
 
 // Owner of position i in a CSR with offsets off[0..n]: the last node whose row starts at or before i
@@ -214,6 +225,11 @@ struct DevSnap {
   uint64_t hmask;            // n_slots - 1
   const uint32_t* hbits;     // holder bitmap over subject ids: bit s set <=> some row holds subject id s
   uint32_t hbits_n;          // bits in hbits (max held subject id + 1); nullptr / 0: not built
+  // holder signatures, hbits_n entries of hsig_w bits (8: u8, 16: u16): entry s = OR of hsig_bit(key) over the
+  // holders of subject id s and their ancestors through radj -- a root whose bit is clear cannot reach s at
+  // any depth; 0 <=> the hbits bit is clear.  nullptr: not built (namespace program, sharded, KG_HSIG_BITS=0)
+  const uint8_t* hsig;
+  uint32_t hsig_w;
   // hash-sharded mode: this snapshot holds the rows of the nodes with shard_owner == shard_rank
   uint32_t shard_rank, shard_n;
   const uint8_t* nowner;  // [n_nodes] owner rank of every node (shard_n > 1)

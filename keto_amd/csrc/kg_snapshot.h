@@ -335,6 +335,7 @@ struct Snapshot {
   int level_events = 0;
   // k_expand_gw: longest wait (us) of a large slot for a small slot's hand-on before it gives its ticket up
   uint32_t expand_gw_wait_us = 100000;
+  int holder_sig = 1;  // kg_snapshot_tune("holder_sig"): k_resolve prunes by the holder signatures (0: the bitmap only; tests, A/B)
   uint32_t stream_steal = 4;   // kg_snapshot_tune("stream_steal"): XCD ranges a k_stream4 wave dequeues from (1..8)
   // Occupancy defaults (library-wide, measured with several batches in flight, the way a server keeps
   // them: C2 and C3 A/Bs in profiles/r2gw_tier_wgs_sweep.jsonl, r2v_occupancy_sweep.jsonl,

@@ -197,6 +197,64 @@ __global__ void k_hold_bits(const uint32_t* key, uint64_t n, uint32_t* bits) {
     if (k < SET_BIT && (i == 0 || k != key[i - 1])) atomicOr(&bits[k >> 5], 1u << (k & 31));
   }
 }
+// ---- holder signatures (DevSnap::hsig).  Entries of `width` (8 or 16) bits packed in u32 words, entry i
+// at bit (i % per) * width of word i / per (per = 32 / width) -- the u8 / u16 element i that k_resolve
+// loads; updates are 32-bit atomicOr on the containing word.
+__device__ __forceinline__ uint32_t hsig_get(const uint32_t* w, uint32_t i, uint32_t width) {
+  const uint32_t per = 32 / width;
+  return (w[i / per] >> ((i % per) * width)) & ((1u << width) - 1);
+}
+__device__ __forceinline__ uint32_t hsig_or(uint32_t* w, uint32_t i, uint32_t width, uint32_t bits) {
+  const uint32_t per = 32 / width, sh = (i % per) * width;
+  return (atomicOr(&w[i / per], bits << sh) >> sh) & ((1u << width) - 1);
+}
+// Node signatures A[v], first the node's own bit (one thread per word)
+__global__ void k_hsig_init(const uint32_t* __restrict__ nd_ns, const uint32_t* __restrict__ nd_rel,
+                            const uint32_t* __restrict__ nd_obj, uint32_t n, uint32_t width, uint32_t* A) {
+  const uint32_t per = 32 / width, words = (n + per - 1) / per;
+  for (uint32_t wi = blockIdx.x * blockDim.x + threadIdx.x; wi < words; wi += gridDim.x * blockDim.x) {
+    uint32_t w = 0;
+    for (uint32_t k = 0, v = wi * per; k < per && v < n; k++, v++)
+      w |= hsig_bit(nmap_key(nd_ns[v], nd_rel[v], nd_obj[v]), width) << (k * width);
+    A[wi] = w;
+  }
+}
+// One pass of A[child] |= A[parent] over every set edge (src[e] -> adj[e]: radj holds exactly these edges,
+// reversed), one thread per edge -- a thread per node would wait for the longest parents list.  In place:
+// OR is monotone, so a read that misses a concurrent update only leaves work for the next pass; the passes
+// end when one changes nothing (cycles converge: every A only grows, within `width` bits).
+__global__ void k_hsig_pass(const uint32_t* __restrict__ adj, const uint32_t* __restrict__ src, uint64_t n_edges,
+                            uint32_t width, uint32_t* A, uint32_t* changed) {
+  bool any = false;
+  for (uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; e < n_edges; e += (uint64_t)gridDim.x * blockDim.x) {
+    const uint32_t c = adj[e], a = hsig_get(A, src[e], width);
+    if (a & ~hsig_get(A, c, width)) any |= (a & ~hsig_or(A, c, width, a)) != 0;
+  }
+  if (any) *changed = 1u;
+}
+// Subject signatures from the sorted (subject, holder) pairs: hsig[u] |= A[holder], subject ids only.  A thread
+// takes HSIG_RUN consecutive pairs and issues one atomic per word it meets (a word covers `per` subjects and
+// the pairs are sorted by subject: an atomic per pair would hit each word ~20 times in a row).
+constexpr uint64_t HSIG_RUN = 16;
+__global__ void k_hsig_subjects(const uint32_t* __restrict__ key, const uint32_t* __restrict__ node, uint64_t n,
+                                uint32_t width, const uint32_t* __restrict__ A, uint32_t* hsig) {
+  const uint32_t per = 32 / width;
+  const uint64_t nch = (n + HSIG_RUN - 1) / HSIG_RUN;
+  for (uint64_t c = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; c < nch; c += (uint64_t)gridDim.x * blockDim.x) {
+    uint32_t wi = NONE, acc = 0;
+    for (uint64_t i = c * HSIG_RUN, ie = min(n, i + HSIG_RUN); i < ie; i++) {
+      const uint32_t k = key[i];
+      if (k >= SET_BIT) break;  // tagged subjects sort after every subject id
+      if (k / per != wi) {
+        if (acc) atomicOr(&hsig[wi], acc);
+        wi = k / per;
+        acc = 0;
+      }
+      acc |= hsig_get(A, node[i], width) << ((k % per) * width);
+    }
+    if (acc) atomicOr(&hsig[wi], acc);
+  }
+}
 __device__ __forceinline__ uint64_t hold_slot(uint32_t key, uint64_t mask) { return mix64(key) & mask; }
 // run starts insert (subject -> first index); run ends then add the count
 __global__ void k_hold_insert(const uint32_t* key, uint64_t n, HSlot* hs, uint64_t mask) {
@@ -603,6 +661,8 @@ int Snapshot::build_reverse() {
   ds.radj = nullptr;
   ds.hbits = nullptr;
   ds.hbits_n = 0;
+  ds.hsig = nullptr;
+  ds.hsig_w = 0;
   if (R >= 0xFFFFFFFFull || nn == 0) return 0;
   uint64_t* roff = nullptr;
   uint32_t* radj = nullptr;
@@ -618,6 +678,20 @@ int Snapshot::build_reverse() {
   HIPC(tmp.reserve(tmp_bytes + 16));
   HIPC(hipcub::DeviceScan::ExclusiveSum(tmp, tmp_bytes, (uint64_t*)deg.get(), roff, (size_t)nn + 1, stream));
   HIPC(hipMemcpyAsync(deg, roff, ((size_t)nn + 1) * 8, hipMemcpyDeviceToDevice, stream));
+  // Holder signatures (DevSnap::hsig) only where k_resolve's no-holder answer is sound without a walk: one
+  // rank, no namespace program.  KG_HSIG_BITS in the environment at build: 0 = none, 8 = u8 entries, else 16
+  // (u16: 16 bits beat 8 in every pair of the headline A/B, profiles/hsig_ab.jsonl).
+  uint32_t sig_w = 16;
+  if (const char* e = getenv("KG_HSIG_BITS")) sig_w = atoi(e) == 0 ? 0u : atoi(e) == 8 ? 8u : 16u;
+  if (has_program || shard_n > 1) sig_w = 0;
+  // node signatures A[v]: the bits of v and of every node above it -- a temporary, alive until the subject
+  // signatures are folded from it below
+  DevBuf<uint32_t> nsig;
+  if (sig_w) {
+    HIPC(nsig.reserve(((size_t)nn * sig_w + 31) / 32));
+    hipLaunchKernelGGL(k_hsig_init, dim3(4096), dim3(256), 0, stream, ds.nd_ns, ds.nd_rel, ds.nd_obj, nn, sig_w, nsig.get());
+    HIPC(hipGetLastError());
+  }
   if (E) {
     DevBuf<uint32_t> src;
     HIPC(src.reserve(E));
@@ -627,6 +701,25 @@ int Snapshot::build_reverse() {
                        ds.adj, (const uint32_t*)src.get(), E, deg, radj);
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(stream));
+    if (sig_w) {
+      // passes until one changes nothing: about the longest chain of nested sets.  Past HSIG_PASSES every
+      // node gets every bit: the signatures then say held / unheld only, which stays correct
+      constexpr int HSIG_PASSES = 64;
+      DevBuf<uint32_t> changed;
+      HIPC(changed.reserve(1));
+      uint32_t h_changed = 1;
+      for (int pass = 0; pass < HSIG_PASSES && h_changed; pass++) {
+        HIPC(hipMemsetAsync(changed, 0, 4, stream));
+        hipLaunchKernelGGL(k_hsig_pass, dim3((uint32_t)std::min<uint64_t>(65536, (E + 255) / 256)), dim3(256), 0, stream,
+                           ds.adj, (const uint32_t*)src.get(), E, sig_w, nsig.get(), changed.get());
+        HIPC(hipGetLastError());
+        HIPC(hipMemcpyAsync(&h_changed, changed, 4, hipMemcpyDeviceToHost, stream));
+        HIPC(hipStreamSynchronize(stream));
+      }
+      if (h_changed) {
+        HIPC(hipMemsetAsync(nsig, 0xFF, nsig.cap() * 4, stream));
+      }
+    }
   }
   HIPC(hipGetLastError());
   HIPC(hipStreamSynchronize(stream));
@@ -668,6 +761,17 @@ int Snapshot::build_reverse() {
     hipLaunchKernelGGL(k_hold_bits, dim3(4096), dim3(256), 0, stream, kb.Current(), R, hbits);
     HIPC(hipGetLastError());
   }
+  // subject signatures: one entry per subject id below nbits, like the bitmap.  Not for an id range so sparse
+  // that the table would outweigh the holders list it summarises (k_resolve then reads the bitmap)
+  uint32_t* hsig = nullptr;
+  const size_t sig_bytes = (((size_t)nbits * sig_w + 31) / 32) * 4;
+  if (sig_w && nbits && sig_bytes <= R * 4 + (1u << 20)) {
+    if (alloc((void**)&hsig, sig_bytes)) return -1;
+    HIPC(hipMemsetAsync(hsig, 0, sig_bytes, stream));
+    hipLaunchKernelGGL(k_hsig_subjects, dim3((uint32_t)std::min<uint64_t>(65536, (R / HSIG_RUN + 256) / 256)), dim3(256), 0,
+                       stream, kb.Current(), vb.Current(), R, sig_w, (const uint32_t*)nsig.get(), hsig);
+    HIPC(hipGetLastError());
+  }
   const uint64_t slots = pow2_at_least(std::max<uint64_t>(16, distinct * 2));
   uint32_t* hold;
   HSlot* hs;
@@ -687,6 +791,8 @@ int Snapshot::build_reverse() {
   ds.hmask = slots - 1;
   ds.hbits = hbits;
   ds.hbits_n = nbits;
+  ds.hsig = reinterpret_cast<const uint8_t*>(hsig);
+  ds.hsig_w = hsig ? sig_w : 0;
   return 0;
 }
 
