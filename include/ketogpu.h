@@ -768,6 +768,61 @@ int kg_lookup_subject_sets_page(kg_snapshot* s, const kg_lookup_subj_set* reqs, 
                                 size_t n, int32_t global_max_depth, kg_lookup_pages* out);
 void kg_lookup_pages_free(kg_lookup_pages* out);
 
+/* ---- access masks ------------------------------------------------------------------------ */
+/* A lookup's answer as one bitmap row per request in caller-owned HBM, for a consumer whose candidates are
+ * already on the GPU (the top-K of a vector search, a ranked feed) and that needs "may this subject see
+ * object o" as a pre-filter or post-filter: nothing but per-request counts and error words crosses the bus.
+ * Defined through the unpaged call: let A_i be the answer of request i from kg_lookup_objects (the first
+ * call) or kg_lookup_subject_sets (the second: id requests with sns == KG_SUBJECT_ID, set requests, or both
+ * in one call).  Row i of the mask is d_mask[i * row_words .. (i + 1) * row_words); bit (o - base) & 31 of
+ * its word (o - base) >> 5 is set exactly when o is in A_i and base <= o < base + n_bits.  Every other bit
+ * of every word of the row is 0 -- the padding bits of the last used word and the words past
+ * ceil(n_bits / 32) too.  The library clears the rows itself: the buffer may hold anything.
+ * n_set[i] is the number of bits set in row i.  n_errors, err_code and the five counters are exactly the
+ * unpaged call's: the range [base, base + n_bits) limits what is WRITTEN, not what is walked or checked --
+ * the call does the unpaged call's whole work, and an error outside the range is still counted.
+ * How: the unpaged call's steps up to its key list (request << 32 | id, unsorted, with duplicates); the
+ * tail then sets one bit per key with an atomic OR, which cares about neither duplicates nor order, so no
+ * sort, no unique step and no id copy follows; one more launch counts the rows.
+ * Arguments: n_bits == 0, row_words < ceil(n_bits / 32), base + n_bits > 0xFFFFFFFF, an n * row_words that
+ * overflows, or a NULL d_mask / out / reqs with n > 0: -2 before any launch.  Hash-sharded snapshots: -3.
+ * n == 0: 0, and nothing is written.
+ * Device and stream: the pointers belong to the device of the snapshot's first replica, and the call
+ * always runs there (no replica rotation), on a stream of the library's.  `stream` is the caller's stream
+ * that last used d_mask (NULL: the buffer is idle, or the null stream used it): the library's stream waits
+ * on an event recorded there before its first write.  The call returns with the mask complete, after a host wait, so work enqueued on
+ * any stream afterwards may read it.  Thread-safe, as the unpaged calls.  out is returned by
+ * kg_lookup_mask_free. */
+typedef struct {
+  uint64_t* n_set;     /* per request: bits set in its row = members with base <= id < base + n_bits */
+  uint64_t* n_errors;  /* per request: as the unpaged call (whole id space, not the range) */
+  uint32_t* err_code;  /* per request: as the unpaged call */
+  uint64_t n_reqs;
+  uint64_t exact, candidates, confirmed, reverse_edges, levels; /* as kg_lookup_buf, same values as the unpaged call */
+  double kernel_ms;
+  uint64_t pinned;     /* library use */
+} kg_lookup_mask_buf;
+int kg_lookup_objects_mask_device(kg_snapshot* s, const kg_lookup* reqs, size_t n, int32_t global_max_depth,
+                                  uint32_t base, uint32_t n_bits, uint32_t* d_mask, size_t row_words,
+                                  kg_lookup_mask_buf* out, void* stream);
+int kg_lookup_subject_sets_mask_device(kg_snapshot* s, const kg_lookup_subj_set* reqs, size_t n,
+                                       int32_t global_max_depth, uint32_t base, uint32_t n_bits,
+                                       uint32_t* d_mask, size_t row_words, kg_lookup_mask_buf* out, void* stream);
+void kg_lookup_mask_free(kg_lookup_mask_buf* out);
+
+/* Ranked select: d_cand holds n rows of k_in ranked ids; row i is run through row i of d_mask (layout as
+ * above; the mask need not come from this snapshot -- s gives the device and the error channel).  An id is
+ * allowed when base <= id < base + n_bits and its bit is set; KG_LOOKUP_END (usable as padding) and every id
+ * outside the range are not.  d_out row i has `limit` entries: the first min(count, limit) allowed ids in
+ * their original order -- duplicates stay as they come -- then KG_LOOKUP_END.  d_count[i] counts every
+ * allowed entry of the row, so it can exceed limit.  k_in == 0 is valid: counts 0, rows all KG_LOOKUP_END.
+ * limit == 0, n_bits == 0, base + n_bits > 0xFFFFFFFF, a row_words below ceil(n_bits / 32) or a NULL pointer
+ * with n > 0 (d_cand may be NULL when k_in == 0): -2.  The call only enqueues on `stream` (NULL: the
+ * snapshot's) and does not wait.  One wave per row; no atomics: the output is deterministic. */
+int kg_mask_select_device(kg_snapshot* s, const uint32_t* d_mask, size_t row_words, uint32_t base, uint32_t n_bits,
+                          const uint32_t* d_cand, size_t n, uint32_t k_in, uint32_t limit,
+                          uint32_t* d_out, uint32_t* d_count, void* stream);
+
 /* ---- tuple listing ----------------------------------------------------------------------- */
 /* GetRelationTuples (GET /relation-tuples, ReadService.ListRelationTuples; relationtuple.Manager over a
  * RelationQuery, internal/persistence/sql/relationtuples.go:124-145,203-244) on the device snapshot:

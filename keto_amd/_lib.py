@@ -125,6 +125,14 @@ class kg_lookup_subj_set(C.Structure):
                 ("srel", C.c_uint32), ("max_depth", C.c_int32)]
 
 
+class kg_lookup_mask_buf(C.Structure):
+    """What a mask call returns on the host: per-request counts and error words, the unpaged call's counters."""
+    _fields_ = [("n_set", C.POINTER(C.c_uint64)), ("n_errors", C.POINTER(C.c_uint64)),
+                ("err_code", C.POINTER(C.c_uint32)), ("n_reqs", C.c_uint64), ("exact", C.c_uint64),
+                ("candidates", C.c_uint64), ("confirmed", C.c_uint64), ("reverse_edges", C.c_uint64),
+                ("levels", C.c_uint64), ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
+
+
 KG_Q_NS, KG_Q_OBJ, KG_Q_REL, KG_Q_SUBJECT = 1, 2, 4, 8
 
 
@@ -164,7 +172,9 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
            "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free",
            "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free",
-           "kg_lookup_subject_sets", "kg_lookup_subject_sets_page"]
+           "kg_lookup_subject_sets", "kg_lookup_subject_sets_page",
+           "kg_lookup_objects_mask_device", "kg_lookup_subject_sets_mask_device", "kg_lookup_mask_free",
+           "kg_mask_select_device"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -258,6 +268,15 @@ def load(path: str = LIB_PATH):
         L.kg_lookup_subject_sets.restype = C.c_int
         L.kg_lookup_subject_sets_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
         L.kg_lookup_subject_sets_page.restype = C.c_int
+    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_objects_mask_device"):
+        # (an A/B build from before the access masks goes without them, as above)
+        for f in (L.kg_lookup_objects_mask_device, L.kg_lookup_subject_sets_mask_device):
+            f.argtypes = [vp, vp, sz, i32, u32, u32, vp, sz, C.POINTER(kg_lookup_mask_buf), vp]
+            f.restype = C.c_int
+        L.kg_lookup_mask_free.argtypes = [C.POINTER(kg_lookup_mask_buf)]
+        L.kg_lookup_mask_free.restype = None
+        L.kg_mask_select_device.argtypes = [vp, vp, sz, u32, u32, vp, sz, u32, u32, vp, vp, vp]
+        L.kg_mask_select_device.restype = C.c_int
     if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_snapshot_holder_sig"):
         L.kg_snapshot_holder_sig.argtypes = [vp]
         L.kg_snapshot_holder_sig.restype = C.c_int

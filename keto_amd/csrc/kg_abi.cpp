@@ -1121,6 +1121,80 @@ void kg_lookup_pages_free(kg_lookup_pages* out) {
   memset(out, 0, sizeof *out);
 }
 
+// The mask calls.  The bitmap's geometry is checked first, before the snapshot is looked at and before any
+// launch.  Then one lane set as lookup_call, but always the lane of replica 0: the caller's pointers belong to
+// that device (as kg_check_batch_device's).
+static int mask_geometry(const char* name, uint32_t base, uint32_t n_bits, size_t row_words) {
+  if (n_bits == 0) return set_error(-2, "%s: n_bits is 0", name);
+  if ((uint64_t)base + n_bits > 0xFFFFFFFFull) return set_error(-2, "%s: base + n_bits exceeds 0xFFFFFFFF", name);
+  if (row_words < ((size_t)n_bits + 31) / 32)
+    return set_error(-2, "%s: row_words %zu holds fewer than n_bits %u bits", name, row_words, n_bits);
+  return 0;
+}
+static int lookup_mask_call(const char* name, kg_snapshot* sp, const void* reqs, size_t n, uint32_t base, uint32_t n_bits,
+                            uint32_t* d_mask, size_t row_words, kg_lookup_mask_buf* out, void* stream,
+                            const std::function<int(Snapshot*, kg::Lane*, const kg::LookupMask&)>& run) {
+  if (out) memset(out, 0, sizeof *out);
+  if (int rc = mask_geometry(name, base, n_bits, row_words)) return rc;
+  if (n && row_words > (SIZE_MAX / 4) / n) return set_error(-2, "%s: n * row_words overflows", name);
+  if (n && !reqs) return set_error(-2, "%s: reqs is NULL", name);
+  if (n && !d_mask) return set_error(-2, "%s: d_mask is NULL", name);
+  if (n && !out) return set_error(-2, "%s: out is NULL", name);
+  if (!sp) return set_error(-2, "%s: NULL snapshot", name);
+  Snapshot* s = reinterpret_cast<Snapshot*>(sp);
+  if (s->shard_n > 1 || kg::shard_comm_of(s, nullptr))
+    return set_error(-3, "%s: not supported on hash-sharded snapshots", name);
+  if (n == 0) return 0;
+  std::vector<kg::Lane*>* lanes = s->lanes_acquire();
+  if (!lanes) return -1;
+  LaneLease lease{s, lanes};
+  kg::Lane* L = (*lanes)[0];
+  std::lock_guard<std::mutex> lk(L->w->mu);
+  return run(L->rep, L, kg::LookupMask{base, n_bits, d_mask, row_words, (hipStream_t)stream, out});
+}
+
+int kg_lookup_objects_mask_device(kg_snapshot* sp, const kg_lookup* reqs, size_t n, int32_t global_max_depth,
+                                  uint32_t base, uint32_t n_bits, uint32_t* d_mask, size_t row_words,
+                                  kg_lookup_mask_buf* out, void* stream) {
+  KG_GUARD_BEGIN
+  return lookup_mask_call("kg_lookup_objects_mask_device", sp, reqs, n, base, n_bits, d_mask, row_words, out, stream,
+                          [&](Snapshot* rep, kg::Lane* L, const kg::LookupMask& m) {
+                            return kg::lookup_objects_mask(rep, L, reqs, n, global_max_depth, m);
+                          });
+  KG_GUARD_END
+}
+
+int kg_lookup_subject_sets_mask_device(kg_snapshot* sp, const kg_lookup_subj_set* reqs, size_t n,
+                                       int32_t global_max_depth, uint32_t base, uint32_t n_bits, uint32_t* d_mask,
+                                       size_t row_words, kg_lookup_mask_buf* out, void* stream) {
+  KG_GUARD_BEGIN
+  return lookup_mask_call("kg_lookup_subject_sets_mask_device", sp, reqs, n, base, n_bits, d_mask, row_words, out,
+                          stream, [&](Snapshot* rep, kg::Lane* L, const kg::LookupMask& m) {
+                            return kg::lookup_subject_sets_mask(rep, L, reqs, n, global_max_depth, m);
+                          });
+  KG_GUARD_END
+}
+
+void kg_lookup_mask_free(kg_lookup_mask_buf* out) {
+  if (out) kg::lookup_mask_free(out);
+}
+
+int kg_mask_select_device(kg_snapshot* sp, const uint32_t* d_mask, size_t row_words, uint32_t base, uint32_t n_bits,
+                          const uint32_t* d_cand, size_t n, uint32_t k_in, uint32_t limit, uint32_t* d_out,
+                          uint32_t* d_count, void* stream) {
+  KG_GUARD_BEGIN
+  const char* name = "kg_mask_select_device";
+  if (limit == 0) return set_error(-2, "%s: limit is 0", name);
+  if (int rc = mask_geometry(name, base, n_bits, row_words)) return rc;
+  if (n > 0x7FFFFFFFull) return set_error(-2, "%s: batch too large", name);
+  if (n && (!d_mask || !d_out || !d_count || (k_in && !d_cand))) return set_error(-2, "%s: NULL pointer", name);
+  if (!sp) return set_error(-2, "%s: NULL snapshot", name);
+  if (n == 0) return 0;
+  return kg::mask_select(reinterpret_cast<Snapshot*>(sp), d_mask, row_words, base, n_bits, d_cand, n, k_in, limit, d_out,
+                         d_count, (hipStream_t)stream);
+  KG_GUARD_END
+}
+
 // A hash-sharded snapshot lists its own rank's rows, as kg_snapshot_rows.
 int kg_snapshot_query(kg_snapshot* sp, const kg_row_query* reqs, size_t n, kg_query_buf* out) {
   KG_GUARD_BEGIN

@@ -63,6 +63,11 @@
 // checked, or its candidates run out.  A walk key above that id stays unplaced: an unchecked candidate may
 // lie below it.  Last, one kernel cuts every request's page out of the sorted unique keys and only the pages
 // go into the pinned block.
+//
+// The mask calls (kg_lookup_objects_mask_device / kg_lookup_subject_sets_mask_device) are the unpaged calls up
+// to their key list and end in Call::finish_mask instead of Call::finish: every key sets its bit in its
+// request's row of the caller's bitmap with an atomicOr, which asks for neither order nor distinct keys, so
+// nothing is sorted, made unique or copied out as ids (k_lk_mask_bits, k_lk_mask_count).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -808,8 +813,41 @@ __global__ __launch_bounds__(256) void k_lk_finish(const u64* __restrict__ uk, u
   }
 }
 
+// ------------------------------------------------------------------ output as access masks
+// The mask tail (Call::finish_mask): row r of the caller's bitmap, `row_words` words, takes bit id - base of
+// every output key request << 32 | id with base <= id < base + n_bits.  The keys come as the steps left them,
+// unsorted and with duplicates (a walk reaches an id through several nodes): an atomicOr sets a bit once
+// however often and in whatever order it is asked to.  rows: the caller's buffer, cleared before this launch.
+__global__ __launch_bounds__(256) void k_lk_mask_bits(const u64* __restrict__ okeys, u64 m, uint32_t n_reqs,
+                                                      uint32_t base, uint32_t n_bits, uint32_t* rows, size_t row_words) {
+  const u64 stride = (u64)gridDim.x * 256;
+  for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < m; i += stride) {
+    const u64 key = okeys[i];
+    const uint32_t r = (uint32_t)(key >> 32), id = (uint32_t)key, d = id - base;
+    if (r >= n_reqs || id < base || d >= n_bits) continue;  // d >> 5 < ceil(n_bits / 32) <= row_words
+    atomicOr(&rows[(size_t)r * row_words + (d >> 5)], 1u << (d & 31));
+  }
+}
+
+// One wave per row, four rows per workgroup: the bits set in the row, and the request's error code out of
+// errmin as k_lk_finish takes it.
+__global__ __launch_bounds__(256) void k_lk_mask_count(const uint32_t* __restrict__ rows, size_t row_words,
+                                                       uint32_t n_reqs, uint64_t* __restrict__ n_set,
+                                                       const u64* __restrict__ errmin, uint32_t* __restrict__ err_code) {
+  const uint32_t r = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= n_reqs) return;  // the whole wave
+  const uint32_t* row = rows + (size_t)r * row_words;
+  u64 c = 0;
+  for (size_t w = lane_id(); w < row_words; w += 64) c += (u64)__popc(row[w]);
+  for (int o = 32; o; o >>= 1) c += shfl64(c, lane_id() ^ o);
+  if (lane_id() == 0) {
+    n_set[r] = c;
+    err_code[r] = errmin[r] == ~0ull ? 0u : (uint32_t)errmin[r];
+  }
+}
+
 // ------------------------------------------------------------------ paged calls: rounds and the page
-constexpr u64 PG_FIRST = 64;            // a request's first round checks at most this many candidates
+constexpr u64 PG_FIRST = 64;           // a request's first round checks at most this many candidates
 constexpr u64 PG_ROUND_MAX = 1ull << 22;  // and no round more than this many of one request
 // The rows one check_batch_device call of a confirmation takes (confirm()).
 // unpaged object candidates: the scan has built every row before the first check; the size was never measured
@@ -993,9 +1031,11 @@ struct LookupBufs {
   DevBuf<u64> ppref, ekeys, pkept, pklo, rkeys, rkeys2;
   DevBuf<uint32_t> ecodes, d_next;
   hipEvent_t ev[2] = {};
+  hipEvent_t mask_ev = nullptr;  // a mask call: where the caller's stream stood when the call came in
   ~LookupBufs() {
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
+    if (mask_ev) (void)hipEventDestroy(mask_ev);
   }
 };
 
@@ -1016,6 +1056,8 @@ struct Call {
   // a paged call: the requests' pages (nullptr: unpaged), the rounds run, the erring keys collected
   const kg_lookup_page* pg = nullptr;
   u64 n_rounds = 0, n_ekeys = 0;
+  // a mask call (unpaged): the answer goes into the caller's bitmap rows instead of id lists (nullptr: lists)
+  const LookupMask* mask = nullptr;
 
   Call(Snapshot* s_, Lane* L, int32_t gmax_)
       : s(s_), w(L->w), st(L->stream), B(*static_cast<LookupBufs*>(L->lk ? L->lk : (L->lk = new LookupBufs()))),
@@ -1111,6 +1153,11 @@ struct Call {
 
   // The end: the keys sorted, duplicates dropped, split by request, the output arrays in one pinned block.
   int finish(kg_lookup_buf* out);
+  // The end of a mask call: the keys as they are -- no sort, no unique step, no count read back -- set their
+  // bits in the caller's rows; only the per-request words cross the bus.
+  int finish_mask();
+  // the end of an unpaged call
+  int end(kg_lookup_buf* out) { return mask ? finish_mask() : finish(out); }
   // the m ids of B.d_objs with B.d_off / n_errors / d_ecode (and d_next: a paged call's next[n]) copied
   // into one pinned block; the call's counters
   int deliver(kg_lookup_buf* out, u64 m, uint32_t** next);
@@ -1206,6 +1253,61 @@ int Call::deliver(kg_lookup_buf* out, u64 m, uint32_t** next) {
   out->reverse_edges = st_edges;
   out->levels = st_levels;
   if (next) *next = o_next;
+  return 0;
+}
+
+int Call::finish_mask() {
+  const LookupMask& M = *mask;
+  kg_lookup_mask_buf* out = M.out;
+  // the lane's first write to the caller's buffer comes after what the caller's stream had enqueued on it
+  // (nullptr: the null stream -- a framework's default stream is that one; nothing to wait for when it is idle)
+  if (!B.mask_ev) HIPC(hipEventCreateWithFlags(&B.mask_ev, hipEventDisableTiming));
+  HIPC(hipEventRecord(B.mask_ev, M.user));
+  HIPC(hipStreamWaitEvent(st, B.mask_ev, 0));
+  HIPC(hipMemsetAsync(M.d_mask, 0, n * M.row_words * 4, st));
+  if (O.have)
+    hipLaunchKernelGGL(k_lk_mask_bits, grid(O.have), dim3(256), 0, st, (const u64*)B.okeys.get(), O.have, (uint32_t)n,
+                       M.base, M.n_bits, M.d_mask, M.row_words);
+  HIPC(B.d_off.reserve(n));  // the rows' counts
+  HIPC(B.d_ecode.reserve(n));
+  hipLaunchKernelGGL(k_lk_mask_count, dim3((uint32_t)((n + 3) / 4)), dim3(256), 0, st, (const uint32_t*)M.d_mask,
+                     M.row_words, (uint32_t)n, B.d_off.get(), (const u64*)B.errmin.get(), B.d_ecode.get());
+  HIPC(hipGetLastError());
+  // one pinned block: n_set[n] | n_errors[n] | err_code[n]
+  const size_t bytes = (size_t)n * 8 + (size_t)n * 8 + (size_t)n * 4;
+  char* blk = (char*)tree_pool_get(bytes);
+  if (!blk) return set_error(KG_ERR_RESOURCE_CODE, "lookup: pinned output allocation failed");
+  uint64_t* o_nset = (uint64_t*)blk;
+  uint64_t* o_nerr = o_nset + n;
+  uint32_t* o_ecode = (uint32_t*)(o_nerr + n);
+  int rc = 0;
+  if (hipMemcpyAsync(o_nset, B.d_off.get(), n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(o_nerr, B.n_errors.get(), n * 8, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(o_ecode, B.d_ecode.get(), n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipEventRecord(B.ev[1], st) != hipSuccess)
+    rc = set_error(-1, "lookup: D2H copy failed");
+  if (!rc) rc = w->wait(st, true);  // the mask is complete when the call returns
+  float ms = 0;
+  if (!rc && hipEventElapsedTime(&ms, B.ev[0], B.ev[1]) != hipSuccess) {
+    (void)hipGetLastError();
+    ms = 0;
+  }
+  if (rc) {
+    (void)hipStreamSynchronize(st);
+    tree_pool_put(blk, bytes);
+    return rc;
+  }
+  out->n_set = o_nset;
+  out->n_errors = o_nerr;
+  out->err_code = o_ecode;
+  out->n_reqs = n;
+  out->exact = n_exact;
+  out->candidates = n_cand;
+  out->confirmed = n_conf;
+  out->reverse_edges = st_edges;
+  out->levels = st_levels;
+  out->kernel_ms = ms;
+  out->pinned = bytes;
   return 0;
 }
 
@@ -1754,7 +1856,7 @@ int unpaged_objects_tail(Call& c, u64 n_rows, kg_lookup_buf* out) {
   };
   if (int rc = confirm<false>(c, n_rows + m, CHUNK_OBJECTS, true, key_rows, ErrCount{B.n_errors.get(), B.errmin.get()}))
     return rc;
-  return c.finish(out);
+  return c.end(out);
 }
 
 // ------------------------------------------------------------------ host: the steps of a subject lookup
@@ -1898,7 +2000,7 @@ int unpaged_subjects_tail(Call& c, const std::vector<uint32_t>& conf, const uint
     return 0;
   };
   if (int rc = confirm<true>(c, nk, CHUNK_SUBJECTS, false, key_rows, sink)) return rc;
-  return c.finish(out);
+  return c.end(out);
 }
 
 }  // namespace
@@ -1908,9 +2010,10 @@ void lookup_bufs_free(void* p) { delete static_cast<LookupBufs*>(p); }
 // kg_lookup_objects on lane L (its stream and workspace; the caller holds the workspace's mutex).  pages:
 // kg_lookup_objects_page -- the same steps, with the candidates as keys checked in rounds, into pout.
 static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lookup_page* pages, size_t n,
-                             int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
+                             int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout, const LookupMask* mask = nullptr) {
   Call c(s, L, gmax);
   c.pg = pages;
+  c.mask = mask;
   const LReq* lr = nullptr;
   const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &lr, [&](uint32_t blocks, const kg_lookup* d_req, LReq* d_lr) {
@@ -1941,9 +2044,10 @@ static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const 
 // root there, and what those list is checked; the others by a check of every subject id of the domain, or of
 // every subject set of their filter's domain.
 static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, const kg_lookup_page* pages, size_t n,
-                              int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout) {
+                              int32_t gmax, kg_lookup_buf* out, kg_lookup_pages* pout, const LookupMask* mask = nullptr) {
   Call c(s, L, gmax);
   c.pg = pages;
+  c.mask = mask;
   const DevSnap& ds = s->ds;
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
   const uint64_t n_rows = s->n_check_rows;
@@ -2003,6 +2107,19 @@ int lookup_objects_page(Snapshot* s, Lane* L, const kg_lookup* reqs, const kg_lo
 int lookup_subjects_page(Snapshot* s, Lane* L, const kg_lookup_subj* reqs, const kg_lookup_page* pages, size_t n,
                          int32_t gmax, kg_lookup_pages* out) {
   return lookup_subjects_on(s, L, id_requests(reqs, n).data(), pages, n, gmax, &out->list, out);
+}
+
+// The mask calls: the unpaged steps, ending in Call::finish_mask.
+int lookup_objects_mask(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t gmax, const LookupMask& mask) {
+  return lookup_objects_on(s, L, reqs, nullptr, n, gmax, nullptr, nullptr, &mask);
+}
+int lookup_subject_sets_mask(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, size_t n, int32_t gmax,
+                             const LookupMask& mask) {
+  return lookup_subjects_on(s, L, reqs, nullptr, n, gmax, nullptr, nullptr, &mask);
+}
+void lookup_mask_free(kg_lookup_mask_buf* out) {
+  if (out->pinned) tree_pool_put(out->n_set, (size_t)out->pinned);
+  memset(out, 0, sizeof *out);
 }
 
 void lookup_free(kg_lookup_buf* out) {

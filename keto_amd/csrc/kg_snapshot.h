@@ -499,6 +499,25 @@ int lookup_subject_sets_page(Snapshot* s, Lane* L, const kg_lookup_subj_set* req
                              int32_t global_max_depth, kg_lookup_pages* out);
 void lookup_free(kg_lookup_buf* out);
 void lookup_bufs_free(void* bufs);
+// the mask calls (kg_lookup_objects_mask_device / kg_lookup_subject_sets_mask_device): the unpaged call with its
+// answer as bitmap rows in the caller's HBM (arguments checked by the caller); `user`: the caller's stream that
+// last used d_mask, nullptr: the buffer is idle
+struct LookupMask {
+  uint32_t base, n_bits;
+  uint32_t* d_mask;
+  size_t row_words;
+  hipStream_t user;
+  kg_lookup_mask_buf* out;
+};
+int lookup_objects_mask(Snapshot* s, Lane* L, const kg_lookup* reqs, size_t n, int32_t global_max_depth,
+                        const LookupMask& mask);
+int lookup_subject_sets_mask(Snapshot* s, Lane* L, const kg_lookup_subj_set* reqs, size_t n, int32_t global_max_depth,
+                             const LookupMask& mask);
+void lookup_mask_free(kg_lookup_mask_buf* out);
+// kg_mask.hip: kg_mask_select_device (arguments checked by the caller); enqueues on st and returns
+int mask_select(Snapshot* s, const uint32_t* d_mask, size_t row_words, uint32_t base, uint32_t n_bits,
+                const uint32_t* d_cand, size_t n, uint32_t k_in, uint32_t limit, uint32_t* d_out, uint32_t* d_count,
+                hipStream_t st);
 // kg_query.hip: kg_snapshot_query on lane L (the caller holds L->w->mu); query_free returns its output
 int query_rows(Snapshot* s, Lane* L, const kg_row_query* reqs, size_t n, kg_query_buf* out);
 void query_free(kg_query_buf* out);

@@ -599,6 +599,114 @@ class Engine:
         return self._page_names(ids, err, nerr, nxt)
 
 
+    # ---- access masks: a lookup's answer as bitmap rows in HBM, and the ranked select through them
+    def _mask_device(self):
+        import torch
+        return torch.device("cuda", getattr(self.snapshot, "devices", [self.snapshot.device])[0])
+
+    def _mask_call(self, call: str, reqs: np.ndarray, base: int, n_bits: Optional[int], out, with_stats: bool):
+        import torch
+        dev = self._mask_device()
+        n = reqs.shape[0]
+        if n_bits is None:
+            n_bits = self.snapshot.interner.n_objects
+        if out is None:
+            out = torch.empty((n, (int(n_bits) + 31) // 32), dtype=torch.int32, device=dev)
+        elif out.dtype != torch.int32 or out.device != dev or out.dim() != 2 or out.shape[0] != n \
+                or not out.is_contiguous():
+            raise ValueError(f"out: a contiguous int32 tensor of {n} rows on {dev}")
+        buf = _lib.kg_lookup_mask_buf()
+        L = _lib.load()
+        _lib.check(getattr(L, call)(self.snapshot.handle, _ptr(reqs) if n else None, n, self.config.max_read_depth,
+                                    int(base), int(n_bits), C.c_void_p(out.data_ptr()), out.shape[1], C.byref(buf),
+                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), call)
+        try:
+            n_set = np.ctypeslib.as_array(buf.n_set, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            err = np.ctypeslib.as_array(buf.err_code, shape=(n,)).copy() if n else np.zeros(0, np.uint32)
+            nerr = np.ctypeslib.as_array(buf.n_errors, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            self.last_stats = {k: getattr(buf, k) for k in ("exact", "candidates", "confirmed", "reverse_edges",
+                                                            "levels", "kernel_ms")} if with_stats else None
+        finally:
+            L.kg_lookup_mask_free(C.byref(buf))
+        return out, n_set, err, nerr
+
+    def lookup_objects_mask_ids(self, reqs: np.ndarray, base: int = 0, n_bits: Optional[int] = None, out=None,
+                                with_stats: bool = False):
+        """kg_lookup_objects_mask_device: reqs as lookup_objects_ids.  Returns (mask, n_set u64 [n], err_code u32
+        [n], n_errors u64 [n]): mask is a torch.int32 tensor [n, row_words] on the snapshot's device whose row i
+        has bit (o - base) & 31 of word (o - base) >> 5 set exactly for the objects o of request i's answer with
+        base <= o < base + n_bits (None: the interner's object-id count); n_set[i] is the row's popcount;
+        err_code, n_errors and last_stats are lookup_objects_ids' (the range limits what is written, not what
+        is checked).  out: a caller tensor [n, row_words >= ceil(n_bits / 32)] to write instead of a new one;
+        work the current torch stream has enqueued on it is waited for.  The mask is complete on return."""
+        return self._mask_call("kg_lookup_objects_mask_device", np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6),
+                               base, n_bits, out, with_stats)
+
+    def lookup_subject_sets_mask_ids(self, reqs: np.ndarray, base: int = 0, n_bits: Optional[int] = None, out=None,
+                                     with_stats: bool = False):
+        """kg_lookup_subject_sets_mask_device: reqs as lookup_subject_sets_ids (sns == KG_SUBJECT_ID: the row is
+        over subject ids); the result as lookup_objects_mask_ids."""
+        return self._mask_call("kg_lookup_subject_sets_mask_device",
+                               np.ascontiguousarray(reqs, np.uint32).reshape(-1, 6), base, n_bits, out, with_stats)
+
+    def object_mask(self, namespace: str, relation: str, subject, rest_depth: int):
+        """lookup_objects as a 1-D torch.int32 bitmap over the interner's object ids, on the snapshot's device:
+        bit o & 31 of word o >> 5 is set when `subject` has `relation` on the object with id o.  Raises
+        CheckError when the check of any object ends in an error."""
+        it = self.snapshot.interner
+        if isinstance(subject, SubjectSet):
+            sub = list(it.subject_set_ids(subject))
+        else:
+            sub = [SUBJECT_ID, it.obj_id(subject), 0]
+        row = np.asarray([it.ns_id(namespace), it.rel_id(relation), *sub, np.int32(rest_depth).view(np.uint32)],
+                         np.uint32)
+        mask, _, err, nerr = self.lookup_objects_mask_ids(row)
+        if int(nerr[0]):
+            raise CheckError(int(err[0]))
+        return mask[0]
+
+    def mask_select(self, mask, cand, limit: int, base: int = 0, n_bits: Optional[int] = None):
+        """kg_mask_select_device: cand is a torch.int32 tensor [n, k_in] of ranked ids (-1 = KG_LOOKUP_END pads a
+        row), mask [n, row_words] one bitmap row per row of cand (a 1-D mask and a 1-D cand are one row).
+        Returns (out int32 [n, limit], count int32 [n]): out[i] holds the first `limit` ids of cand[i] whose bit
+        is set, in their order, then -1; count[i] is the number of such ids in the whole row.  n_bits None: the
+        interner's object-id count, or the bits the rows hold if that is fewer.  Enqueued on the current torch
+        stream; nothing is copied to the host."""
+        import torch
+        dev = self._mask_device()
+        mask = mask.unsqueeze(0) if mask.dim() == 1 else mask
+        cand = cand.unsqueeze(0) if cand.dim() == 1 else cand
+        for name, t in (("mask", mask), ("cand", cand)):
+            if t.dtype != torch.int32 or t.device != dev or t.dim() != 2 or not t.is_contiguous():
+                raise ValueError(f"{name}: a contiguous 2-D int32 tensor on {dev}")
+        n, k_in = cand.shape
+        if mask.shape[0] != n:
+            raise ValueError("one mask row per row of candidates")
+        if n_bits is None:  # the ids handed out since the mask was written have no bit in it: they are not allowed
+            n_bits = min(self.snapshot.interner.n_objects, 32 * mask.shape[1])
+        out = torch.empty((n, max(int(limit), 0)), dtype=torch.int32, device=dev)
+        count = torch.empty((n,), dtype=torch.int32, device=dev)
+        cur = torch.cuda.current_stream(dev)
+        # the library takes a NULL stream for its own: on torch's default stream the select runs on a side
+        # stream of this engine that is ordered behind and ahead of the current one
+        side = None
+        if cur.cuda_stream == 0:
+            side = getattr(self, "_mask_side", None)
+            if side is None:
+                side = self._mask_side = torch.cuda.Stream(dev)
+            side.wait_stream(cur)
+        run = side if side is not None else cur
+        _lib.check(_lib.load().kg_mask_select_device(
+            self.snapshot.handle, C.c_void_p(mask.data_ptr()), mask.shape[1], int(base), int(n_bits),
+            C.c_void_p(cand.data_ptr()), n, k_in, int(limit), C.c_void_p(out.data_ptr()), C.c_void_p(count.data_ptr()),
+            C.c_void_p(run.cuda_stream)), "kg_mask_select_device")
+        if side is not None:
+            cur.wait_stream(side)
+            for t in (mask, cand, out, count):
+                t.record_stream(side)
+        return out, count
+
+
 class ExpandEngine:
     """expand.Engine: subject-set trees."""
 

@@ -92,6 +92,11 @@ class Interner:
     def n_relations(self) -> int:
         return len(self._rel_names)
 
+    @property
+    def n_objects(self) -> int:
+        """Object / subject ids handed out so far: every id is below it (the width of an access mask)."""
+        return len(self._obj_names)
+
     # ---- tuples
     def tuple_ids(self, t: RelationTuple) -> Tuple[int, int, int, int, int, int]:
         ns, obj, rel = self.ns_id(t.namespace), self.obj_id(t.object), self.rel_id(t.relation)
