@@ -879,6 +879,49 @@ typedef struct {
 int kg_snapshot_query(kg_snapshot* s, const kg_row_query* reqs, size_t n, kg_query_buf* out);
 void kg_query_free(kg_query_buf* out);
 
+/* ---- delete by query --------------------------------------------------------------------- */
+/* DeleteAllRelationTuples (DELETE /admin/relation-tuples, WriteService.DeleteRelationTuples;
+ * internal/persistence/sql/relationtuples.go:146-162,187-201: one DELETE ... WHERE over the query's
+ * conditions) as a refresh of the device snapshot: *out = base's rows minus every row that matches ANY of
+ * the n queries.  It is the one write that is not a tuple delta -- the persister never learns which rows
+ * went -- so the caller sends the query itself instead of paging the matches out for kg_snapshot_apply.
+ * Match: exactly kg_snapshot_query's for (mask, t): fields not named in mask are ignored; KG_Q_SUBJECT with
+ * t.sns == KG_SUBJECT_ID matches subject-id rows only, anything else only rows with exactly that subject
+ * set (`...` sets are rows like any other); an id that fits no node or occurs in no row matches nothing
+ * and is not an error; mask == 0 matches every row.  Raw rows only, never a materialised union's merged
+ * check rows.  `after` and `limit` are ignored: the reference's delete has no page.
+ * Result: the kept rows keep their order and their order keys, node ids do not change (a node whose last
+ * row went stays behind with an empty row, as after kg_snapshot_apply).  Everything else as
+ * kg_snapshot_apply: each replica is rebuilt on its own device, the base stays valid for its readers and
+ * hands its host node map on to *out, dict and prog are used as there, and the call must not run
+ * concurrently with another apply or delete on the same base.
+ * res: matched[i] = base rows query i matches (a row that several queries match counts for each);
+ * n_deleted = distinct rows removed; with KG_DELETE_KEYS, keys[0 .. n_deleted) = the removed rows' order
+ * keys as kg_snapshot_query reports them (position + 1 in kg_snapshot_export's order on a snapshot without
+ * keys), ascending, duplicates kept.  Return res with kg_delete_free.
+ * Nothing matched, or n == 0: returns 0 with *out = NULL and n_deleted = 0; no snapshot is built on any
+ * replica and the base keeps its node map.
+ * Failures, before any launch: a NULL base, out or res, NULL q with n > 0, n > KG_DELETE_MAX_QUERIES or an
+ * unknown flag bit is -2; so is a hash-sharded snapshot (it rebuilds).
+ * Cost: one pass over all row entries (4 B read and 4 B written each, the node triples once where a query
+ * names a node field; temporaries of 4 B + 8 B per entry) plus the rebuild of every derived structure, as
+ * after kg_snapshot_apply.  It is never cheaper than that, however few rows match.  kernel_ms covers the
+ * match and the compaction, not the derived structures. */
+#define KG_DELETE_MAX_QUERIES 64
+#define KG_DELETE_KEYS 1u          /* flags: also return the deleted rows' order keys */
+typedef struct {
+  uint64_t* matched;    /* per query: base rows it matches (a row matched by several queries counts for each) */
+  uint64_t* keys;       /* n_deleted order keys of the deleted rows, ascending, duplicates kept; NULL without KG_DELETE_KEYS */
+  uint64_t n_queries, n_deleted;   /* n_deleted: distinct rows removed */
+  uint64_t rows_scanned;
+  double kernel_ms;     /* match + compaction (HIP events); not the derived structures */
+  uint64_t pinned;      /* library use */
+} kg_delete_buf;
+int kg_snapshot_delete_matching(kg_snapshot* base, const kg_row_query* q, size_t n, uint32_t flags,
+                                const kg_dict* dict, const kg_rewrite_prog* prog,
+                                kg_snapshot** out, kg_delete_buf* res);
+void kg_delete_free(kg_delete_buf* res);
+
 /* ---- errors ----------------------------------------------------------------------------- */
 /* Thread-local text of the last failing call; returns its length. */
 size_t kg_last_error(char* buf, size_t len);

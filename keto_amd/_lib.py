@@ -147,6 +147,16 @@ class kg_query_buf(C.Structure):
                 ("kernel_ms", C.c_double), ("pinned", C.c_uint64)]
 
 
+KG_DELETE_MAX_QUERIES = 64
+KG_DELETE_KEYS = 1
+
+
+class kg_delete_buf(C.Structure):
+    _fields_ = [("matched", C.POINTER(C.c_uint64)), ("keys", C.POINTER(C.c_uint64)), ("n_queries", C.c_uint64),
+                ("n_deleted", C.c_uint64), ("rows_scanned", C.c_uint64), ("kernel_ms", C.c_double),
+                ("pinned", C.c_uint64)]
+
+
 # kg_row_query as a numpy record (48 B: the u64 is 8-aligned)
 ROW_QUERY_DTYPE = np.dtype({"names": ["mask", "t", "after", "limit"],
                             "formats": ["<u4", ("<u4", (6,)), "<u8", "<u4"],
@@ -174,7 +184,7 @@ EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic
            "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free",
            "kg_lookup_subject_sets", "kg_lookup_subject_sets_page",
            "kg_lookup_objects_mask_device", "kg_lookup_subject_sets_mask_device", "kg_lookup_mask_free",
-           "kg_mask_select_device"]
+           "kg_mask_select_device", "kg_snapshot_delete_matching", "kg_delete_free"]
 
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
@@ -284,6 +294,12 @@ def load(path: str = LIB_PATH):
     L.kg_snapshot_query.restype = C.c_int
     L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]
     L.kg_query_free.restype = None
+    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_snapshot_delete_matching"):
+        # (an A/B build from before the delete-by-query refresh goes without it, as above)
+        L.kg_snapshot_delete_matching.argtypes = [vp, vp, sz, u32, vp, vp, C.POINTER(vp), C.POINTER(kg_delete_buf)]
+        L.kg_snapshot_delete_matching.restype = C.c_int
+        L.kg_delete_free.argtypes = [C.POINTER(kg_delete_buf)]
+        L.kg_delete_free.restype = None
     L.kg_tree_free.argtypes = [C.POINTER(kg_tree_buf)]
     L.kg_tree_free.restype = None
     L.kg_last_error.argtypes = [C.c_char_p, sz]

@@ -150,6 +150,74 @@ int kg_snapshot_apply(kg_snapshot* bp, const kg_tuple* ins, const uint64_t* ins_
   KG_GUARD_END
 }
 
+// The match runs first, on replica 0's device: when nothing matches, no replica builds anything.  Replica 0
+// then compacts with that match; every other replica repeats it on its own device.
+int kg_snapshot_delete_matching(kg_snapshot* bp, const kg_row_query* q, size_t n, uint32_t flags, const kg_dict* dict,
+                                const kg_rewrite_prog* prog, kg_snapshot** out, kg_delete_buf* res) {
+  KG_GUARD_BEGIN
+  const char* name = "kg_snapshot_delete_matching";
+  if (!bp || !out || !res) return set_error(-2, "%s: NULL argument", name);
+  *out = nullptr;
+  memset(res, 0, sizeof *res);
+  if (n && !q) return set_error(-2, "%s: q is NULL", name);
+  if (n > KG_DELETE_MAX_QUERIES) return set_error(-2, "%s: %zu queries, at most %d a call", name, n, KG_DELETE_MAX_QUERIES);
+  if (flags & ~KG_DELETE_KEYS) return set_error(-2, "%s: unknown flag bits 0x%x", name, flags & ~KG_DELETE_KEYS);
+  Snapshot* base = reinterpret_cast<Snapshot*>(bp);
+  if (base->shard_n > 1) return set_error(-2, "kg_snapshot_apply: sharded snapshots rebuild instead");
+  kg::clear_error();
+  if (n == 0) return 0;
+  const bool want_keys = (flags & KG_DELETE_KEYS) != 0;
+  kg::DeleteMatch m;
+  {
+    if (hipSetDevice(base->device) != hipSuccess) return set_error(-1, "hipSetDevice(%d) failed", base->device);
+    hipStream_t st = nullptr;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) return set_error(-1, "hipStreamCreate failed");
+    const int rc = kg::delete_match(base, st, q, n, want_keys, &m);
+    (void)hipStreamDestroy(st);
+    if (rc) return rc;
+  }
+  const uint64_t gone = m.total - m.kept;
+  const size_t bytes = (n + (want_keys ? (size_t)gone : 0)) * 8;
+  uint64_t* blk = (uint64_t*)kg::tree_pool_get(bytes);
+  if (!blk) return set_error(kg::KG_ERR_RESOURCE_CODE, "%s: pinned output allocation failed", name);
+  res->matched = blk;
+  res->pinned = bytes;
+  res->n_queries = n;
+  res->rows_scanned = m.total;
+  memcpy(res->matched, m.matched.data(), n * 8);
+  if (!gone) {
+    res->kernel_ms = m.ms;
+    return 0;
+  }
+  int rc = 0;
+  if (want_keys) {
+    res->keys = blk + n;
+    if (hipMemcpy(res->keys, m.d_keys, (size_t)gone * 8, hipMemcpyDeviceToHost) != hipSuccess)
+      rc = set_error(-1, "%s: reading the deleted keys back failed", name);
+  }
+  if (!rc) {
+    std::vector<int> devs;
+    for (size_t i = 0; i < base->n_replicas(); i++) devs.push_back(base->replica(i)->device);
+    rc = build_replicas(devs.data(), (int)devs.size(), [&](Snapshot* s, int i) {
+      return s->create_from_delete(base->replica((size_t)i), q, n, i == 0 ? &m : nullptr, dict, prog);
+    }, out);
+  }
+  if (rc) {
+    kg_delete_free(res);
+    return rc;
+  }
+  res->n_deleted = gone;
+  res->kernel_ms = m.ms;
+  return 0;
+  KG_GUARD_END
+}
+
+void kg_delete_free(kg_delete_buf* res) {
+  if (!res) return;
+  if (res->matched && res->pinned) kg::tree_pool_put(res->matched, (size_t)res->pinned);
+  memset(res, 0, sizeof *res);
+}
+
 int kg_snapshot_create(const kg_tuple* rows, size_t n, const kg_dict* dict, const kg_rewrite_prog* prog, int device_mask,
                        kg_snapshot** out) {
   const std::vector<int> d = mask_devices(device_mask);

@@ -391,12 +391,7 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
     HIPC(hipGetLastError());
   }
   HIPC(hipMemsetAsync(d_keep + F, 0, 4, stream));
-  // (the scratch for every scan below: the largest of them)
-  const uint64_t n_rows_max = base->h_row_off_last + iv.size();
-  size_t tb3 = 0;
-  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb3, (const uint32_t*)nullptr, (uint64_t*)nullptr, (size_t)n_rows_max + 1,
-                                        stream));
-  tb = std::max(tb, tb3);
+  // (the scratch for both scans below: the larger of them)
   if (tmp.alloc(&scratch, tb + 16)) return -1;
   HIPC(hipcub::DeviceScan::ExclusiveSum(scratch, tb, d_keep, d_kr, (size_t)F + 1, stream));
   if (n_t) {
@@ -427,10 +422,22 @@ int Snapshot::create_from_delta(Snapshot* base, const kg_tuple* ins, const uint6
                        base->ds.row_off, base->d_row_key, n0, D, (const uint32_t*)d_tslot, (const uint64_t*)d_toff,
                        (const uint64_t*)d_kr, (const uint64_t*)d_ro, d_rs, d_row_key);
   HIPC(hipGetLastError());
+  return derive_from_rows(d_ro, d_rs, d_ns, d_obj, d_rel, total, dict, prog);
+}
+
+// Steps 5 to 7 of a refresh, whatever made the new rows (the delta above, kg_delete.hip's compaction).
+int Snapshot::derive_from_rows(uint64_t* d_ro, uint32_t* d_rs, uint32_t* d_ns, uint32_t* d_obj, uint32_t* d_rel,
+                               uint64_t total, const kg_dict* dict, const kg_rewrite_prog* prog) {
+  const uint32_t n1 = ds.n_nodes;
+  DevTemps tmp;
   // 5. set-adjacency: a flag per row entry, scanned into positions
   uint32_t* flag;
   uint64_t* pos;
-  if (tmp.alloc((void**)&flag, total * 4 + 8) || tmp.alloc((void**)&pos, (total + 1) * 8)) return -1;
+  void* scratch;
+  size_t tb = 0;
+  HIPC(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (const uint32_t*)nullptr, (uint64_t*)nullptr, (size_t)total + 1, stream));
+  if (tmp.alloc((void**)&flag, total * 4 + 8) || tmp.alloc((void**)&pos, (total + 1) * 8) || tmp.alloc(&scratch, tb + 16))
+    return -1;
   if (total)
     hipLaunchKernelGGL(k_delta_isadj, dim3(2048), dim3(256), 0, stream, (const uint32_t*)d_rs, total,
                        (const uint32_t*)d_rel, wildcard_rel, flag);

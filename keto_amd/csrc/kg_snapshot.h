@@ -259,6 +259,18 @@ struct Lane {
   ~Lane();
 };
 
+// kg_delete.hip: one replica's match of a delete-by-query on its device -- a keep flag per row entry of
+// the base and the flags' exclusive scan -- and what the call reports from it.
+struct DeleteMatch {
+  DevTemps tmp;
+  uint32_t* keep = nullptr;  // [total + 1]: 0 = the entry matches a query
+  uint64_t* kr = nullptr;    // [total + 1]: kept entries before each; kr[total] = kept
+  uint64_t total = 0, kept = 0;
+  std::vector<uint64_t> matched;     // per query
+  const uint64_t* d_keys = nullptr;  // the deleted entries' order keys, ascending (asked for and total > kept)
+  double ms = 0;                     // device time so far: match, scan, keys; then the compaction
+};
+
 struct Snapshot {
   int device = -1;
   int n_cu = 256;
@@ -393,6 +405,14 @@ struct Snapshot {
   // kg_delta.hip: this snapshot = base's rows + inserted - deleted, built on the device
   int create_from_delta(Snapshot* base, const kg_tuple* ins, const uint64_t* ins_keys, size_t n_ins,
                         const kg_tuple* del, size_t n_del, const kg_dict* dict, const kg_rewrite_prog* prog);
+  // kg_delete.hip: this snapshot = base's rows minus the ones a query matches.  pre: the match already
+  // made on this device (released once the rows are compacted), or nullptr: made here
+  int create_from_delete(Snapshot* base, const kg_row_query* q, size_t n, DeleteMatch* pre, const kg_dict* dict,
+                         const kg_rewrite_prog* prog);
+  // kg_delta.hip: the rest of a refresh, from the new rows (ds.n_nodes set, every array an alloc() of
+  // this snapshot): set adjacency, program, flags, materialisation, formulas, live marking, hash tables
+  int derive_from_rows(uint64_t* d_ro, uint32_t* d_rs, uint32_t* d_ns, uint32_t* d_obj, uint32_t* d_rel, uint64_t total,
+                       const kg_dict* dict, const kg_rewrite_prog* prog);
   int device_flags();  // purity closure on the device (rewrite / undeclared relations reachable)
   int create_synthetic(const kg_synth_params* p, const kg_rewrite_prog* prog);
   int upload_program(const kg_dict* dict, const kg_rewrite_prog* prog);
@@ -522,6 +542,9 @@ int mask_select(Snapshot* s, const uint32_t* d_mask, size_t row_words, uint32_t 
 int query_rows(Snapshot* s, Lane* L, const kg_row_query* reqs, size_t n, kg_query_buf* out);
 void query_free(kg_query_buf* out);
 void query_bufs_free(void* bufs);
+// kg_delete.hip: kg_snapshot_delete_matching's match of q[0, n) on `base`'s rows, on stream st of base's
+// device (the current one); waits for it.  want_keys: also m->d_keys
+int delete_match(Snapshot* base, hipStream_t st, const kg_row_query* q, size_t n, bool want_keys, DeleteMatch* m);
 constexpr uint64_t KG_TREE_DEVICE = 0x100;  // kg_tree_buf.pinned: device-resident trees (low byte: the device)
 void* tree_dev_get(int device, size_t bytes);  // device memory for device-resident tree outputs
 void tree_dev_put(int device, void* p, size_t bytes);

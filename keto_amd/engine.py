@@ -131,6 +131,42 @@ class Snapshot:
         new.devices = getattr(self, "devices", [self.device])
         return new
 
+    def delete_matching(self, reqs: np.ndarray, want_keys: bool = False, with_stats: bool = False):
+        """kg_snapshot_delete_matching (DeleteAllRelationTuples on the device): a new snapshot holding this
+        one's rows minus every row that matches any of `reqs` (kg_row_query records, row_queries() builds
+        them; `after` and `limit` are ignored; at most KG_DELETE_MAX_QUERIES).  Returns (snapshot or None
+        when no row matched, matched u64 [n] per query, the deleted rows' order keys u64 [m] ascending or
+        None without want_keys) and, with_stats, a dict of n_deleted / rows_scanned / kernel_ms.  This
+        snapshot stays valid for readers; the next refresh goes to the returned one."""
+        L = _lib.load()
+        it = self.interner
+        reqs = np.ascontiguousarray(reqs, dtype=_lib.ROW_QUERY_DTYPE).reshape(-1)
+        n = reqs.shape[0]
+        d = _lib.kg_dict(it.n_namespaces, it.n_relations, it.wildcard_rel)
+        new = Snapshot(None, it, self.program, self.device, _handle=C.c_void_p())
+        prog_c = new._prog(self.program)
+        pc = C.byref(prog_c) if prog_c is not None else None
+        h = C.c_void_p()
+        buf = _lib.kg_delete_buf()
+        _lib.check(L.kg_snapshot_delete_matching(self._h, _ptr(reqs) if n else None, n,
+                                                 _lib.KG_DELETE_KEYS if want_keys else 0, C.byref(d), pc, C.byref(h),
+                                                 C.byref(buf)), "kg_snapshot_delete_matching")
+        try:
+            m = int(buf.n_deleted)
+            matched = np.ctypeslib.as_array(buf.matched, shape=(n,)).copy() if n else np.zeros(0, np.uint64)
+            keys = None
+            if want_keys:
+                keys = np.ctypeslib.as_array(buf.keys, shape=(m,)).copy() if m else np.zeros(0, np.uint64)
+            stats = {"n_deleted": m, "rows_scanned": int(buf.rows_scanned), "kernel_ms": float(buf.kernel_ms)}
+        finally:
+            L.kg_delete_free(C.byref(buf))
+        if h.value:
+            new._h = h
+            new.devices = getattr(self, "devices", [self.device])
+        else:
+            new = None
+        return (new, matched, keys, stats) if with_stats else (new, matched, keys)
+
     @classmethod
     def synthetic(cls, n_tuples: int, seed: int = 20250131, device: int = 0, n_layers: int = 8,
                   max_degree: int = 100000, set_fraction: float = 0.25, doc_set_fraction: float = 0.5,

@@ -7,11 +7,13 @@ rule, status mirroring and the response shapes, as the reference's handlers do t
                                                     internal/check/handler.go:101-232
         GET /relation-tuples/expand                 internal/expand/handler.go:81-107
         GET /relation-tuples                        internal/relationtuple/read_server.go:122-175
+        DELETE /admin/relation-tuples               internal/relationtuple/transact_server.go:152-181
         GET /relation-tuples/list-objects           no reference counterpart (ListObjectsHandler)
         GET /relation-tuples/list-subjects          no reference counterpart (ListSubjectsHandler)
   gRPC  CheckService.Check                          internal/check/handler.go:234-275
         ExpandService.Expand                        internal/expand/handler.go:109-146
         ReadService.ListRelationTuples              internal/relationtuple/read_server.go:65-102
+        WriteService.DeleteRelationTuples           internal/relationtuple/transact_server.go:64-85
 
 An unknown namespace is "not allowed" over REST (handler.go:156-160, 221-225) but an error over gRPC
 (:261-264, the mapper's herodot.ErrNotFound).  Request errors are herodot's 400s
@@ -461,13 +463,13 @@ def _subject_proto(t: RelationTuple) -> dict:
 
 class RelationTuplesHandler:
     """internal/relationtuple/read_server.go: REST GET /relation-tuples and gRPC ListRelationTuples over one
-    relationtuple.Manager (a SnapshotPersister, host or device reads)."""
+    relationtuple.Manager (a SnapshotPersister, host or device reads); of transact_server.go, the
+    delete-by-query pair: REST DELETE /admin/relation-tuples and gRPC DeleteRelationTuples."""
 
     def __init__(self, manager, mapper: Mapper):
         self.manager, self.mapper = manager, mapper
 
-    def _list(self, query, page_token: str, page_size: int):
-        from .persister import MalformedPageToken
+    def _map_query(self, query) -> None:
         try:  # Mapper.FromQuery (uuid_mapping.go:60-120): the namespaces that are named must exist
             if query.namespace is not None:
                 self.mapper.check_namespace(query.namespace)
@@ -475,6 +477,10 @@ class RelationTuplesHandler:
                 self.mapper.check_namespace(query.subject_set.namespace)
         except NamespaceNotFound as e:
             raise HandlerError(404, f"Unable to locate the resource: namespace {e.args[0]!r}")
+
+    def _list(self, query, page_token: str, page_size: int):
+        from .persister import MalformedPageToken
+        self._map_query(query)
         try:
             return self.manager.get_relation_tuples(query, page_token, page_size)
         except MalformedPageToken:
@@ -502,6 +508,18 @@ class RelationTuplesHandler:
         """ReadService.ListRelationTuples (read_server.go:65-102): req = {"relation_query": {...}} or the
         deprecated {"query": {...}} whose empty strings mean unset, each with an optional "subject"
         ({"id"} | {"set": {...}}), plus "page_size" and "page_token".  Raises HandlerError on failure."""
+        rq = self._query_from_proto(req)
+        if rq is None:
+            raise _bad("you must provide a query")
+        tuples, token = self._list(rq, str(req.get("page_token", "")), int(req.get("page_size", 0)))
+        return {"relation_tuples": [{"namespace": t.namespace, "object": t.object, "relation": t.relation,
+                                     "subject": _subject_proto(t)} for t in tuples],
+                "next_page_token": token}
+
+    @staticmethod
+    def _query_from_proto(req: dict):
+        """RelationQuery.FromDataProvider over req["relation_query"], or over the deprecated req["query"]
+        (whose empty strings mean unset); None with neither."""
         from .persister import RelationQuery
         if req.get("relation_query") is not None:
             src = req["relation_query"]
@@ -510,7 +528,7 @@ class RelationTuplesHandler:
             src = req["query"]
             ns, obj, rel = (src.get(k) or None for k in ("namespace", "object", "relation"))
         else:
-            raise _bad("you must provide a query")
+            return None
         sub = src.get("subject") or {}
         sid, sset = None, None
         if "id" in sub:
@@ -518,8 +536,26 @@ class RelationTuplesHandler:
         elif "set" in sub:
             s = sub.get("set") or {}
             sset = SubjectSet(s.get("namespace", ""), s.get("object", ""), s.get("relation", ""))
-        tuples, token = self._list(RelationQuery(ns, obj, rel, sid, sset), str(req.get("page_token", "")),
-                                   int(req.get("page_size", 0)))
-        return {"relation_tuples": [{"namespace": t.namespace, "object": t.object, "relation": t.relation,
-                                     "subject": _subject_proto(t)} for t in tuples],
-                "next_page_token": token}
+        return RelationQuery(ns, obj, rel, sid, sset)
+
+    # ---- DELETE /admin/relation-tuples, WriteService.DeleteRelationTuples
+    def delete_relations(self, query: Union[str, Query]) -> Tuple[int, Optional[dict]]:
+        """DELETE /admin/relation-tuples?namespace=&object=&relation=&subject_id= | subject_set.*=
+        (transact_server.go:152-181): every tuple the query matches goes; 204 without a body."""
+        try:
+            rq = relation_query_from_url_query(parse_query(query))
+            self._map_query(rq)
+            self.manager.delete_all_relation_tuples(rq)
+        except HandlerError as e:
+            return e.status, e.body()
+        return 204, None
+
+    def grpc_delete_relation_tuples(self, req: dict) -> dict:
+        """WriteService.DeleteRelationTuples (transact_server.go:64-85): req = {"relation_query": {...}} or
+        the deprecated {"query": {...}}, as grpc_list_relation_tuples reads them.  Raises HandlerError."""
+        rq = self._query_from_proto(req)
+        if rq is None:
+            raise _bad("invalid request")
+        self._map_query(rq)
+        self.manager.delete_all_relation_tuples(rq)
+        return {}

@@ -25,7 +25,10 @@ sees every committed write (read-your-writes).  The first snapshot, and any delt
 ``rebuild_fraction`` of the rows, is a full ``kg_snapshot_create_ordered``.  Reads of the tuple
 list (``get_relation_tuples``) are answered from the host rows, or -- ``device_reads=True`` -- from
 the refreshed snapshot (``kg_snapshot_query``: the filter and the page selection run on the device,
-the host maps one page of ids back to strings).  Shard
+the host maps one page of ids back to strings).  ``delete_all_relation_tuples`` walks the host
+rows and queues the matching tuples as deletes, or -- ``device_deletes=True`` -- sends the query to
+the snapshot (``kg_snapshot_delete_matching``: match and compaction run on the device, the host
+removes the rows under the returned shard-id keys).  Shard
 ids come from a seeded generator so runs are reproducible (the reference draws them from
 crypto/rand; only their order matters, and no reference test pins it).
 """
@@ -91,8 +94,11 @@ class SnapshotPersister:
 
     def __init__(self, namespaces: Sequence[Namespace] = (), max_read_depth: int = 5, device: int = 0,
                  seed: int = 0, interner: Optional[Interner] = None, devices: Optional[Sequence[int]] = None,
-                 rebuild_fraction: float = 0.125, device_reads: bool = False):
+                 rebuild_fraction: float = 0.125, device_reads: bool = False, device_deletes: bool = False):
         self.device_reads = device_reads  # get_relation_tuples from the snapshot instead of the host rows
+        # delete_all_relation_tuples on the snapshot (kg_snapshot_delete_matching) instead of a pass over the host rows
+        self.device_deletes = device_deletes
+        self.device_deletes_done = 0  # deletes that built a snapshot
         self.interner = interner or Interner()
         self.namespaces = list(namespaces)
         self.config = Config(max_read_depth, self.namespaces)
@@ -152,11 +158,38 @@ class SnapshotPersister:
 
     def delete_all_relation_tuples(self, query: RelationQuery) -> None:
         with self._lock:
+            if self.device_deletes:
+                return self._device_delete(query)
             gone = {t for _, t in self._rows if query.matches(t)}
             for t in gone:
                 self._remove_tuple(t)
             if gone:
                 self._version += 1
+
+    def _device_delete(self, query: RelationQuery) -> None:
+        """The delete where the rows live (kg_snapshot_delete_matching): the refreshed snapshot drops the
+        matching rows and reports their order keys; the host rows under those keys follow.  No pass over
+        the host rows, and no tuple delta: the returned snapshot is the current one."""
+        snap = self.snapshot()  # the pending delta is in it
+        ids = self._query_ids(query)
+        if ids is None:
+            return
+        new, _, keys = snap.delete_matching(row_queries([ids[0]], [ids[1]]), want_keys=True)
+        if new is None:
+            return
+        low = (1 << 64) - 1
+        for k in np.unique(keys).tolist():  # the key is the shard id's high half (_key)
+            for sid, t in list(self._rows.irange_key(min_key=k << 64, max_key=(k << 64) | low)):
+                if not query.matches(t):
+                    continue
+                self._rows.remove((sid, t))
+                left = self._by_tuple[t]
+                left.remove(sid)
+                if not left:
+                    del self._by_tuple[t]
+        self._version += 1
+        self._snap, self._snap_version = new, self._version
+        self.device_deletes_done += 1
 
     # ---- reads of the tuple list
     def get_relation_tuples(self, query: RelationQuery, page_token: str = "",
@@ -184,11 +217,9 @@ class SnapshotPersister:
             token = str(res[-1][0])
         return [t for _, t in res], token
 
-    def _device_page(self, query: RelationQuery, last: int, per_page: int) -> Tuple[List[RelationTuple], str]:
-        """One page from the refreshed snapshot.  Strings map without interning: a string no tuple ever
-        had matches nothing.  The order key is the shard id's high half (_key), so is `after`; the token is
-        the full shard id of the page's last row, found in the host rows by its key."""
-        snap = self.snapshot()  # every committed write is in it
+    def _query_ids(self, query: RelationQuery) -> Optional[Tuple[int, List[int]]]:
+        """The query as a kg_row_query's (mask, tuple ids), mapped without interning; None where a string
+        was never seen: no row can match."""
         it = self.interner
         mask, t = 0, [0] * 6
         try:
@@ -206,7 +237,19 @@ class SnapshotPersister:
                 t[3:6] = it.ns_id(ss.namespace, create=False), it.obj_id(ss.object, create=False), \
                     it.rel_id(ss.relation, create=False)
         except KeyError:
+            return None
+        return mask, t
+
+    def _device_page(self, query: RelationQuery, last: int, per_page: int) -> Tuple[List[RelationTuple], str]:
+        """One page from the refreshed snapshot.  Strings map without interning: a string no tuple ever
+        had matches nothing.  The order key is the shard id's high half (_key), so is `after`; the token is
+        the full shard id of the page's last row, found in the host rows by its key."""
+        snap = self.snapshot()  # every committed write is in it
+        it = self.interner
+        ids = self._query_ids(query)
+        if ids is None:
             return [], ""
+        mask, t = ids
         rows, keys, _, nxt, _ = snap.query(row_queries([mask], [t], self._key(last), per_page))
         res = [it.relation_tuple(r) for r in rows]
         token = ""
