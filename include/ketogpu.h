@@ -246,7 +246,10 @@ int kg_snapshot_info(const kg_snapshot* s, uint64_t* info4);
  * the environment at snapshot creation turns it off. */
 int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
 /* Engine knobs (no reference counterpart; tuning and tests).  Results never depend on any of them.  An
- * unknown key, or a value outside the key's range, returns -2.
+ * unknown key, or a value outside the key's range, returns -2 and changes nothing.  The keys, their defaults and
+ * ranges below restate the table in keto_amd/csrc/kg_knobs.h, which is their source (every key but "grid_reserve"
+ * is one row of it); a key applies to every replica, and a snapshot built from another one (kg_snapshot_apply,
+ * kg_snapshot_delete_matching) starts from the defaults again.
  * Check tiers.  key "stream_ecap" (0..2^32-1, default 512; 0 = no budget): edges a query may enqueue in
  * the stream tier before it is handed to the backward / grid tiers -- cuts the stream kernel's tail of
  * long walks.  key "stream_steal" (1..8, default 4): XCD ranges of the work list a k_stream4 wave
@@ -284,8 +287,8 @@ int kg_snapshot_materialized(const kg_snapshot* s, uint64_t* out3);
  * described with kg_lookup_objects and kg_snapshot_query below (defaults 0, 0, 1, 0).
  * Hash-sharded mode.  key "shard_vis" (10..34, default 23): log2 of the per-batch (query, node) visited
  * table.  "shard_heavy" (0..2^32-1, default 64): set rows longer than this go to k_shard_heavy, which
- * spreads their edges over the grid (0: every row).  "shard_budget" (default 0 = off) /
- * "shard_back_budget" (default 2^14): see kg_shard_back_* below.  "shard_bucket" (0..2^26, default 0 =
+ * spreads their edges over the grid (0: every row).  "shard_budget" (0..2^32-1, default 0 = off) /
+ * "shard_back_budget" (0..2^32-1, default 2^14): see kg_shard_back_* below.  "shard_bucket" (0..2^26, default 0 =
  * sized from the batch): the first bucket size (records per destination) of in-library bindings made
  * after it.  "shard_local" (0/1, default 1), "shard_force_exchange" (0/1, default 0), "shard_remote_meta"
  * (0/1, default 1), "shard_max_reruns" (0..64, default 0 = max(4, exchanges)) and "shard_max_bytes"

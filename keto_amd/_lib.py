@@ -169,23 +169,6 @@ class kg_synth_params(C.Structure):
                 ("preset", C.c_uint32), ("doc_alpha", C.c_float), ("group_alpha", C.c_float)]
 
 
-# every symbol include/ketogpu.h declares
-EXPORTS = ["kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic", "kg_snapshot_synthetic_on",
-           "kg_snapshot_replicas", "kg_snapshot_destroy", "kg_snapshot_info", "kg_snapshot_materialized", "kg_snapshot_tune", "kg_synth_ids",
-           "kg_snapshot_holder_sig", "kg_snapshot_create_ordered", "kg_snapshot_apply",
-           "kg_snapshot_export", "kg_snapshot_rows", "kg_snapshot_export_csr", "kg_check_batch", "kg_check_batch_device", "kg_check_batch_packed_device", "kg_pack_queries_device", "kg_synth_queries",
-           "kg_expand_batch", "kg_expand_batch_device", "kg_tree_free", "kg_last_error", "kg_version", "kg_check_batch_packed", "kg_shard_owner", "kg_snapshot_create_shard",
-           "kg_snapshot_synthetic_shard", "kg_shard_seed", "kg_shard_level", "kg_shard_level_seg", "kg_shard_finish",
-           "kg_shard_done", "kg_shard_levels", "kg_shard_back_list", "kg_shard_back_seed", "kg_shard_back_level", "kg_shard_refwd_seed",
-           "kg_shard_held_words", "kg_shard_held", "kg_shard_result_slots", "kg_shard_bad_nodes", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats", "kg_batcher_reset_stats", "kg_batcher_destroy",
-           "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
-           "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_shard_comm_levels", "kg_check_tree",
-           "kg_lookup_objects", "kg_lookup_subjects", "kg_lookup_free", "kg_snapshot_query", "kg_query_free",
-           "kg_lookup_objects_page", "kg_lookup_subjects_page", "kg_lookup_pages_free",
-           "kg_lookup_subject_sets", "kg_lookup_subject_sets_page",
-           "kg_lookup_objects_mask_device", "kg_lookup_subject_sets_mask_device", "kg_lookup_mask_free",
-           "kg_mask_select_device", "kg_snapshot_delete_matching", "kg_delete_free"]
-
 KG_SHARD_UNIQUE_ID_BYTES = 128
 # kg_shard_transport callbacks (include/ketogpu.h): collective over the ranks, 0 = success
 ALLTOALL2_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -212,6 +195,90 @@ class kg_batcher_stats_t(C.Structure):
                 ("batch_p99_ms", C.c_double), ("call_p50_ms", C.c_double), ("call_p99_ms", C.c_double)]
 
 
+def _bindings() -> dict:
+    vp, sz, i32, u32, u64, i, P = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER
+    return {
+        "kg_version": (C.c_char_p, []),
+        "kg_last_error": (sz, [C.c_char_p, sz]),
+        "kg_snapshot_create": (i, [vp, sz, P(kg_dict), P(kg_rewrite_prog), i, P(vp)]),
+        "kg_snapshot_create_on": (i, [vp, sz, P(kg_dict), P(kg_rewrite_prog), vp, i, P(vp)]),
+        "kg_snapshot_create_ordered": (i, [vp, vp, sz, vp, vp, vp, i, vp]),
+        "kg_snapshot_apply": (i, [vp, vp, vp, sz, vp, sz, vp, vp, vp]),
+        "kg_snapshot_delete_matching": (i, [vp, vp, sz, u32, vp, vp, P(vp), P(kg_delete_buf)]),
+        "kg_delete_free": (None, [P(kg_delete_buf)]),
+        "kg_snapshot_synthetic": (i, [P(kg_synth_params), P(kg_rewrite_prog), i, P(vp)]),
+        "kg_snapshot_synthetic_on": (i, [P(kg_synth_params), P(kg_rewrite_prog), vp, i, P(vp)]),
+        "kg_snapshot_replicas": (i, [vp, vp, i]),
+        "kg_snapshot_destroy": (None, [vp]),
+        "kg_snapshot_info": (i, [vp, vp]),
+        "kg_snapshot_materialized": (i, [vp, vp]),
+        "kg_snapshot_tune": (i, [vp, C.c_char_p, C.c_int64]),
+        "kg_snapshot_holder_sig": (i, [vp]),
+        "kg_synth_ids": (i, [vp, vp]),
+        "kg_snapshot_export": (C.c_int64, [vp, vp, u64]),
+        "kg_snapshot_rows": (C.c_int64, [vp, vp, sz, vp, vp, u64]),
+        "kg_snapshot_export_csr": (i, [vp, vp, vp, vp, vp, vp]),
+        "kg_check_batch": (i, [vp, vp, sz, i32, vp, vp, P(kg_stats)]),
+        "kg_check_batch_packed": (i, [vp, vp, sz, i32, vp, vp, vp, sz, P(sz), P(kg_stats)]),
+        "kg_check_batch_device": (i, [vp, vp, sz, i32, vp, vp, P(kg_stats), vp]),
+        "kg_check_batch_packed_device": (i, [vp, vp, sz, i32, vp, vp, P(kg_stats), vp]),
+        "kg_pack_queries_device": (i, [vp, vp, sz, vp, vp]),
+        "kg_synth_queries": (i, [vp, u64, sz, vp]),
+        "kg_check_tree": (i, [vp, vp, i32, vp, sz, vp, sz, P(sz), P(C.c_uint8), P(u32)]),
+        "kg_expand_batch": (i, [vp, vp, sz, i32, P(kg_tree_buf)]),
+        "kg_expand_batch_device": (i, [vp, vp, sz, i32, P(kg_tree_buf), vp]),
+        "kg_tree_free": (None, [P(kg_tree_buf)]),
+        "kg_lookup_objects": (i, [vp, vp, sz, i32, P(kg_lookup_buf)]),
+        "kg_lookup_subjects": (i, [vp, vp, sz, i32, P(kg_lookup_buf)]),
+        "kg_lookup_subject_sets": (i, [vp, vp, sz, i32, P(kg_lookup_buf)]),
+        "kg_lookup_free": (None, [P(kg_lookup_buf)]),
+        "kg_lookup_objects_page": (i, [vp, vp, vp, sz, i32, P(kg_lookup_pages)]),
+        "kg_lookup_subjects_page": (i, [vp, vp, vp, sz, i32, P(kg_lookup_pages)]),
+        "kg_lookup_subject_sets_page": (i, [vp, vp, vp, sz, i32, P(kg_lookup_pages)]),
+        "kg_lookup_pages_free": (None, [P(kg_lookup_pages)]),
+        "kg_lookup_objects_mask_device": (i, [vp, vp, sz, i32, u32, u32, vp, sz, P(kg_lookup_mask_buf), vp]),
+        "kg_lookup_subject_sets_mask_device": (i, [vp, vp, sz, i32, u32, u32, vp, sz, P(kg_lookup_mask_buf), vp]),
+        "kg_lookup_mask_free": (None, [P(kg_lookup_mask_buf)]),
+        "kg_mask_select_device": (i, [vp, vp, sz, u32, u32, vp, sz, u32, u32, vp, vp, vp]),
+        "kg_snapshot_query": (i, [vp, vp, sz, P(kg_query_buf)]),
+        "kg_query_free": (None, [P(kg_query_buf)]),
+        "kg_batcher_create": (i, [vp, i32, sz, u32, i, P(vp)]),
+        "kg_batcher_check": (i, [vp, vp, sz, vp, vp]),
+        "kg_batcher_stats": (i, [vp, P(kg_batcher_stats_t)]),
+        "kg_batcher_reset_stats": (None, [vp]),
+        "kg_batcher_destroy": (None, [vp]),
+        "kg_shard_owner": (u32, [u32, u32, u32]),
+        "kg_snapshot_create_shard": (i, [vp, sz, P(kg_dict), P(kg_rewrite_prog), i, u32, u32, P(vp)]),
+        "kg_snapshot_synthetic_shard": (i, [P(kg_synth_params), P(kg_rewrite_prog), i, u32, u32, P(vp)]),
+        "kg_shard_seed": (i, [vp, vp, sz, i32, vp, sz, vp, vp, vp, vp]),
+        "kg_shard_level": (i, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
+        "kg_shard_level_seg": (i, [vp, vp, u32, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
+        "kg_shard_levels": (i, [vp, i32, vp, vp, sz, vp, vp, i32, vp, vp, sz, i32, P(i32), vp]),
+        "kg_shard_done": (i, [vp, sz, vp, vp, i, vp, u32, vp]),
+        "kg_shard_back_list": (i, [vp, sz, vp, vp, vp, sz, vp, vp]),
+        "kg_shard_back_seed": (i, [vp, vp, sz, vp, vp, sz, vp, vp]),
+        "kg_shard_back_level": (i, [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, u32, vp]),
+        "kg_shard_refwd_seed": (i, [vp, sz, vp, vp, vp, sz, vp, vp]),
+        "kg_shard_held_words": (i, [vp, vp]),
+        "kg_shard_held": (i, [vp, vp, sz, i, vp]),
+        "kg_shard_finish": (i, [vp, sz, vp, vp, vp]),
+        "kg_shard_result_slots": (sz, [vp, sz]),
+        "kg_shard_bad_nodes": (i, [vp, vp]),
+        "kg_shard_unique_id": (i, [vp]),
+        "kg_shard_comm_init": (i, [vp, vp, i, i, vp]),
+        "kg_shard_transport_attach": (i, [vp, P(kg_shard_transport), vp]),
+        "kg_shard_comm_release": (i, [vp, vp]),
+        "kg_shard_comm_stats": (i, [vp, vp, vp]),
+        "kg_shard_comm_stats_ex": (i, [vp, vp, vp, sz]),
+        "kg_shard_comm_levels": (C.c_int64, [vp, vp, vp, sz]),
+    }
+
+
+# every symbol include/ketogpu.h declares: name -> (restype, argtypes)
+BINDINGS = _bindings()
+EXPORTS = list(BINDINGS)
+
+
 class KetoGPUError(RuntimeError):
     pass
 
@@ -227,134 +294,14 @@ def load(path: str = LIB_PATH):
         raise KetoGPUError(f"libketogpu.so not found at {path}: build it with `python -m keto_amd.build` "
                            "(there is no CPU fallback)")
     L = C.CDLL(path)
-    vp, sz, i32, u32, u64 = C.c_void_p, C.c_size_t, C.c_int32, C.c_uint32, C.c_uint64
-    L.kg_snapshot_create.argtypes = [vp, sz, C.POINTER(kg_dict), C.POINTER(kg_rewrite_prog), C.c_int, C.POINTER(vp)]
-    L.kg_snapshot_create_on.argtypes = [vp, sz, C.POINTER(kg_dict), C.POINTER(kg_rewrite_prog), vp, C.c_int,
-                                        C.POINTER(vp)]
-    L.kg_snapshot_synthetic.argtypes = [C.POINTER(kg_synth_params), C.POINTER(kg_rewrite_prog), C.c_int,
-                                        C.POINTER(vp)]
-    L.kg_snapshot_synthetic_on.argtypes = [C.POINTER(kg_synth_params), C.POINTER(kg_rewrite_prog), vp, C.c_int,
-                                           C.POINTER(vp)]
-    L.kg_snapshot_replicas.argtypes = [vp, vp, C.c_int]
-    L.kg_snapshot_destroy.argtypes = [vp]
-    L.kg_snapshot_destroy.restype = None
-    L.kg_snapshot_info.argtypes = [vp, vp]
-    L.kg_snapshot_create_ordered.argtypes = [vp, vp, sz, vp, vp, vp, C.c_int, vp]
-    L.kg_snapshot_apply.argtypes = [vp, vp, vp, sz, vp, sz, vp, vp, vp]
-    L.kg_snapshot_materialized.argtypes = [vp, vp]
-    L.kg_synth_ids.argtypes = [vp, vp]
-    L.kg_snapshot_tune.argtypes = [vp, C.c_char_p, C.c_int64]
-    L.kg_snapshot_export.argtypes = [vp, vp, u64]
-    L.kg_snapshot_export.restype = C.c_int64
-    L.kg_snapshot_rows.argtypes = [vp, vp, sz, vp, vp, u64]
-    L.kg_snapshot_rows.restype = C.c_int64
-    L.kg_snapshot_export_csr.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.kg_snapshot_export_csr.restype = C.c_int
-    L.kg_check_batch.argtypes = [vp, vp, sz, i32, vp, vp, C.POINTER(kg_stats)]
-    L.kg_check_batch_device.argtypes = [vp, vp, sz, i32, vp, vp, C.POINTER(kg_stats), vp]
-    L.kg_check_batch_packed.argtypes = [vp, vp, sz, i32, vp, vp, vp, sz, C.POINTER(sz), C.POINTER(kg_stats)]
-    L.kg_check_batch_packed_device.argtypes = [vp, vp, sz, i32, vp, vp, C.POINTER(kg_stats), vp]
-    L.kg_pack_queries_device.argtypes = [vp, vp, sz, vp, vp]
-    L.kg_synth_queries.argtypes = [vp, u64, sz, vp]
-    L.kg_expand_batch.argtypes = [vp, vp, sz, i32, C.POINTER(kg_tree_buf)]
-    L.kg_expand_batch_device.argtypes = [vp, vp, sz, i32, C.POINTER(kg_tree_buf), vp]
-    L.kg_lookup_objects.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
-    L.kg_lookup_objects.restype = C.c_int
-    L.kg_lookup_subjects.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
-    L.kg_lookup_subjects.restype = C.c_int
-    L.kg_lookup_free.argtypes = [C.POINTER(kg_lookup_buf)]
-    L.kg_lookup_free.restype = None
-    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_objects_page"):
-        # (an A/B build from before the paged calls, loaded through KG_LIB_PATH, goes without them)
-        L.kg_lookup_objects_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
-        L.kg_lookup_objects_page.restype = C.c_int
-        L.kg_lookup_subjects_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
-        L.kg_lookup_subjects_page.restype = C.c_int
-        L.kg_lookup_pages_free.argtypes = [C.POINTER(kg_lookup_pages)]
-        L.kg_lookup_pages_free.restype = None
-    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_subject_sets"):
-        # (an A/B build from before the subject-set lookup goes without it, as above)
-        L.kg_lookup_subject_sets.argtypes = [vp, vp, sz, i32, C.POINTER(kg_lookup_buf)]
-        L.kg_lookup_subject_sets.restype = C.c_int
-        L.kg_lookup_subject_sets_page.argtypes = [vp, vp, vp, sz, i32, C.POINTER(kg_lookup_pages)]
-        L.kg_lookup_subject_sets_page.restype = C.c_int
-    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_lookup_objects_mask_device"):
-        # (an A/B build from before the access masks goes without them, as above)
-        for f in (L.kg_lookup_objects_mask_device, L.kg_lookup_subject_sets_mask_device):
-            f.argtypes = [vp, vp, sz, i32, u32, u32, vp, sz, C.POINTER(kg_lookup_mask_buf), vp]
-            f.restype = C.c_int
-        L.kg_lookup_mask_free.argtypes = [C.POINTER(kg_lookup_mask_buf)]
-        L.kg_lookup_mask_free.restype = None
-        L.kg_mask_select_device.argtypes = [vp, vp, sz, u32, u32, vp, sz, u32, u32, vp, vp, vp]
-        L.kg_mask_select_device.restype = C.c_int
-    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_snapshot_holder_sig"):
-        L.kg_snapshot_holder_sig.argtypes = [vp]
-        L.kg_snapshot_holder_sig.restype = C.c_int
-    L.kg_snapshot_query.argtypes = [vp, vp, sz, C.POINTER(kg_query_buf)]
-    L.kg_snapshot_query.restype = C.c_int
-    L.kg_query_free.argtypes = [C.POINTER(kg_query_buf)]
-    L.kg_query_free.restype = None
-    if path == os.path.join(HERE, "lib", "libketogpu.so") or hasattr(L, "kg_snapshot_delete_matching"):
-        # (an A/B build from before the delete-by-query refresh goes without it, as above)
-        L.kg_snapshot_delete_matching.argtypes = [vp, vp, sz, u32, vp, vp, C.POINTER(vp), C.POINTER(kg_delete_buf)]
-        L.kg_snapshot_delete_matching.restype = C.c_int
-        L.kg_delete_free.argtypes = [C.POINTER(kg_delete_buf)]
-        L.kg_delete_free.restype = None
-    L.kg_tree_free.argtypes = [C.POINTER(kg_tree_buf)]
-    L.kg_tree_free.restype = None
-    L.kg_last_error.argtypes = [C.c_char_p, sz]
-    L.kg_last_error.restype = sz
-    L.kg_version.restype = C.c_char_p
-    L.kg_shard_owner.argtypes = [u32, u32, u32]
-    L.kg_shard_owner.restype = u32
-    L.kg_snapshot_create_shard.argtypes = [vp, sz, C.POINTER(kg_dict), C.POINTER(kg_rewrite_prog), C.c_int, u32, u32,
-                                           C.POINTER(vp)]
-    L.kg_snapshot_synthetic_shard.argtypes = [C.POINTER(kg_synth_params), C.POINTER(kg_rewrite_prog), C.c_int, u32,
-                                              u32, C.POINTER(vp)]
-    L.kg_shard_seed.argtypes = [vp, vp, sz, i32, vp, sz, vp, vp, vp, vp]
-    L.kg_shard_level.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, C.c_uint32, vp]
-    L.kg_shard_level_seg.argtypes = [vp, vp, C.c_uint32, sz, vp, vp, sz, vp, vp, vp, vp, C.c_uint32, vp]
-    L.kg_shard_level_seg.restype = C.c_int
-    L.kg_shard_done.argtypes = [vp, sz, vp, vp, C.c_int, vp, C.c_uint32, vp]
-    L.kg_shard_levels.argtypes = [vp, i32, vp, vp, sz, vp, vp, i32, vp, vp, sz, i32, C.POINTER(i32), vp]
-    L.kg_shard_levels.restype = C.c_int
-    L.kg_shard_back_list.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp]
-    L.kg_shard_back_seed.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp]
-    L.kg_shard_back_level.argtypes = [vp, vp, sz, vp, vp, sz, vp, vp, vp, vp, C.c_uint32, vp]
-    L.kg_shard_refwd_seed.argtypes = [vp, sz, vp, vp, vp, sz, vp, vp]
-    L.kg_shard_held_words.argtypes = [vp, vp]
-    L.kg_shard_held.argtypes = [vp, vp, sz, C.c_int, vp]
-    L.kg_shard_bad_nodes.argtypes = [vp, vp]
-    L.kg_shard_result_slots.argtypes = [vp, sz]
-    L.kg_shard_result_slots.restype = sz
-    L.kg_shard_finish.argtypes = [vp, sz, vp, vp, vp]
-    L.kg_shard_unique_id.argtypes = [vp]
-    L.kg_shard_comm_init.argtypes = [vp, vp, C.c_int, C.c_int, vp]
-    L.kg_shard_transport_attach.argtypes = [vp, C.POINTER(kg_shard_transport), vp]
-    L.kg_shard_comm_release.argtypes = [vp, vp]
-    L.kg_shard_comm_stats.argtypes = [vp, vp, vp]
-    L.kg_shard_comm_stats_ex.argtypes = [vp, vp, vp, sz]
-    L.kg_shard_comm_levels.argtypes = [vp, vp, vp, sz]
-    L.kg_shard_comm_levels.restype = C.c_int64
-    L.kg_check_tree.argtypes = [vp, vp, i32, vp, sz, vp, sz, C.POINTER(sz), C.POINTER(C.c_uint8), C.POINTER(u32)]
-    L.kg_batcher_create.argtypes = [vp, i32, sz, u32, C.c_int, C.POINTER(vp)]
-    L.kg_batcher_check.argtypes = [vp, vp, sz, vp, vp]
-    L.kg_batcher_stats.argtypes = [vp, C.POINTER(kg_batcher_stats_t)]
-    L.kg_batcher_reset_stats.argtypes = [vp]
-    L.kg_batcher_reset_stats.restype = None
-    L.kg_batcher_destroy.argtypes = [vp]
-    L.kg_batcher_destroy.restype = None
-    for name in ("kg_snapshot_create", "kg_snapshot_create_on", "kg_snapshot_synthetic", "kg_snapshot_synthetic_on",
-                 "kg_snapshot_replicas", "kg_snapshot_info", "kg_snapshot_materialized", "kg_snapshot_tune",
-                 "kg_snapshot_create_ordered", "kg_snapshot_apply", "kg_synth_ids", "kg_check_batch", "kg_check_batch_packed",
-                 "kg_check_batch_device", "kg_check_batch_packed_device", "kg_pack_queries_device", "kg_synth_queries",
-                 "kg_expand_batch", "kg_expand_batch_device", "kg_snapshot_create_shard",
-                 "kg_snapshot_synthetic_shard", "kg_shard_seed", "kg_shard_level", "kg_shard_level_seg", "kg_shard_finish",
-                 "kg_shard_done", "kg_shard_levels", "kg_shard_back_list", "kg_shard_back_seed", "kg_shard_back_level", "kg_shard_refwd_seed",
-                 "kg_shard_held_words", "kg_shard_held", "kg_batcher_create", "kg_batcher_check", "kg_batcher_stats",
-                 "kg_shard_unique_id", "kg_shard_comm_init", "kg_shard_transport_attach", "kg_shard_comm_release",
-                 "kg_shard_comm_stats", "kg_shard_comm_stats_ex", "kg_check_tree"):
-        getattr(L, name).restype = C.c_int
+    own = path == os.path.join(HERE, "lib", "libketogpu.so")
+    for name, (restype, argtypes) in BINDINGS.items():
+        if not hasattr(L, name):
+            if own:
+                raise KetoGPUError(f"{path} does not export {name}: rebuild it with `python -m keto_amd.build --force`")
+            continue  # an older A/B build loaded through KG_LIB_PATH goes without the calls added since
+        f = getattr(L, name)
+        f.restype, f.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -468,200 +468,29 @@ int kg_snapshot_materialized(const kg_snapshot* sp, uint64_t* out3) {
   return 0;
 }
 
+// One key on one replica.  Every key is a row of kg_knobs.h's table, but for the two that act instead of
+// (only) storing: "grid_reserve" allocates, "max_lanes" is read by calls waiting on the lane pool.
 static int tune_one(Snapshot* s, const char* key, int64_t value) {
   std::lock_guard<std::mutex> lk(s->mu);
-
-
-  if (strcmp(key, "shard_vis") == 0) {
-    if (value < 10 || value > 34) return set_error(-2, "shard_vis must be in [10, 34]");
-    s->shard_vis_log2 = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_bucket") == 0) {
-    if (value < 0 || value > (1ll << 26)) return set_error(-2, "shard_bucket must be in [0, 2^26]");
-    s->shard_bucket0 = (uint32_t)value;
-    return 0;
-  }
-
-  if (strcmp(key, "shard_force_exchange") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "shard_force_exchange must be 0 or 1");
-    s->shard_force_exchange = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_local") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "shard_local must be 0 or 1");
-    s->shard_local = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_remote_meta") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "shard_remote_meta must be 0 or 1");
-    s->shard_remote_meta = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_max_reruns") == 0) {
-    if (value < 0 || value > 64) return set_error(-2, "shard_max_reruns must be in [0, 64]");
-    s->shard_max_reruns = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_max_bytes") == 0) {
-    if (value < 0) return set_error(-2, "shard_max_bytes must be >= 0 (0: a quarter of the free HBM)");
-    s->shard_max_bytes = (uint64_t)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_force_overflow") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "shard_force_overflow must be 0 or 1");
-    s->shard_force_overflow = (int)value;
-    return 0;
-  }
-
-  if (strcmp(key, "stream_ecap") == 0) {
-    if (value < 0 || value > 0xFFFFFFFFll) return set_error(-2, "stream_ecap must be in [0, 2^32)");
-    s->stream_ecap = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(key, "shard_budget") == 0) {
-    if (value < 0 || value > 0xFFFFFFFFll) return set_error(-2, "shard_budget must be in [0, 2^32)");
-    s->shard_budget = (uint32_t)value;
-    return 0;
-  }
-
-  if (strcmp(key, "shard_heavy") == 0) {
-    if (value < 0 || value > 0xFFFFFFFFll) return set_error(-2, "shard_heavy must be in [0, 2^32)");
-    s->shard_heavy = (uint32_t)value;
-    return 0;
-  }
-
-
-
-  if (strcmp(key, "shard_back_budget") == 0) {
-    if (value < 0 || value > 0xFFFFFFFFll) return set_error(-2, "shard_back_budget must be in [0, 2^32)");
-    s->shard_back_budget = (uint32_t)value;
-    return 0;
-  }
-
-  if (strcmp(key, "holder_sig") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "holder_sig must be 0 or 1");
-    s->holder_sig = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "stream_steal") == 0) {
-    if (value < 1 || value > 8) return set_error(-2, "stream_steal must be in [1, 8]");
-    s->stream_steal = (uint32_t)value;
-    return 0;
-  }
-
-  if (strcmp(key, "stream_wgs") == 0) {
-    if (value < 0 || value > 8) return set_error(-2, "stream_wgs must be in [0, 8]");
-    s->stream_wgs = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "grid_wgs") == 0) {
-    if (value < 1 || value > 64) return set_error(-2, "grid_wgs must be in [1, 64]");
-    s->grid_wgs = (int)value;
-    return 0;
-  }
-
-  if (strcmp(key, "interp_cap2") == 0) {
-    if (value < 0 || value > (1 << 22)) return set_error(-2, "interp_cap2 must be in [0, 4194304]");
-    s->interp_cap2 = (uint32_t)value;
-    return 0;
-  }
   if (strcmp(key, "grid_reserve") == 0) return kg::grid_reserve(s);  // the shared full-size grid pool, now
-  if (strcmp(key, "grid_cap") == 0) {
-    if (value < 0 || value > (1ll << 34)) return set_error(-2, "grid_cap must be in [0, 2^34]");
-    s->grid_small_cap = (uint64_t)value;
-    return 0;
-  }
-  if (strcmp(key, "expand_gw") == 0 || strcmp(key, "expand_skip_lds") == 0) {
-    if (value < 0 || value > (strcmp(key, "expand_gw") == 0 ? 1 : 2))
-      return set_error(-2, "%s must be 0 or 1 (expand_skip_lds: 0, 1 or 2)", key);
-    (strcmp(key, "expand_gw") == 0 ? s->expand_gw : s->expand_skip_lds) = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "expand_hash_cap") == 0) {
-    if (value < 4 || value > (1 << 18)) return set_error(-2, "expand_hash_cap must be in [4, 2^18]");
-    s->expand_hash_cap = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(key, "level_events") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "level_events must be 0 or 1");
-    s->level_events = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "expand_gw_wait_us") == 0) {
-    if (value < 0 || value > 10000000) return set_error(-2, "expand_gw_wait_us must be in [0, 10^7]");
-    s->expand_gw_wait_us = (uint32_t)value;
-    return 0;
-  }
-
-  if (strcmp(key, "grid_ms") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "grid_ms must be 0 or 1");
-    s->grid_ms = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "grid_ms_bytes") == 0) {
-    if (value < (1 << 20) || value > (1ll << 40)) return set_error(-2, "grid_ms_bytes must be in [2^20, 2^40]");
-    s->grid_ms_bytes = (size_t)value;
-    return 0;
-  }
-  if (strcmp(key, "grid_ms_words") == 0) {
-    if (value != 1 && value != 2 && value != 4 && value != 8 && value != 16)
-      return set_error(-2, "grid_ms_words must be 1, 2, 4, 8 or 16");
-    s->grid_ms_words = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "grid_ms_tg_cap") == 0) {
-    if (value < 0 || value > 0x7FFFFFFF) return set_error(-2, "grid_ms_tg_cap must be in [0, 2^31)");
-    s->grid_ms_tg_cap = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(key, "grid_ms_cap") == 0) {
-    if (value < 0 || value > (1ll << 28)) return set_error(-2, "grid_ms_cap must be in [0, 2^28]");
-    s->grid_ms_cap = (uint64_t)value;
-    return 0;
-  }
-
+  const kg::Knob* k = nullptr;
+  int rc;
   if (strcmp(key, "max_lanes") == 0) {
-    if (value < 1 || value > 1024) return set_error(-2, "max_lanes in [1, 1024]");
     {
-      std::lock_guard<std::mutex> lk(s->lane_mu);
-      s->lane_cap = (size_t)value;  // sets already created stay in the pool
+      std::lock_guard<std::mutex> lk2(s->lane_mu);
+      rc = kg::knob_set(s->knobs, key, value, &k);
     }
-    s->lane_cv.notify_all();
-    return 0;
+    if (!rc) s->lane_cv.notify_all();
+  } else {
+    rc = kg::knob_set(s->knobs, key, value, &k);
   }
-  if (strcmp(key, "lookup_cap") == 0) {
-    if (value < 0 || value > (1ll << 32)) return set_error(-2, "lookup_cap must be in [0, 2^32]");
-    s->lookup_cap = (uint64_t)value;
-    return 0;
+  if (rc == kg::KNOB_UNKNOWN) return set_error(-2, "unknown knob '%s'", key);
+  if (rc == kg::KNOB_OUT_OF_RANGE) {
+    if (k->hi == INT64_MAX) return set_error(-2, "%s must be >= %lld", key, (long long)k->lo);
+    return set_error(-2, "%s must be %s[%lld, %lld]", key, k->kind == kg::KNOB_POW2 ? "a power of two in " : "in ",
+                     (long long)k->lo, (long long)k->hi);
   }
-  if (strcmp(key, "lookup_domain_rows") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "lookup_domain_rows must be 0 or 1");
-    s->lookup_domain_rows = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "lookup_formula") == 0) {
-    if (value < 0 || value > 1) return set_error(-2, "lookup_formula must be 0 or 1");
-    s->lookup_formula = (int)value;
-    return 0;
-  }
-  if (strcmp(key, "query_cap") == 0) {
-    if (value < 0 || value > (1ll << 32)) return set_error(-2, "query_cap must be in [0, 2^32]");
-    s->query_cap = (uint64_t)value;
-    return 0;
-  }
-  if (strcmp(key, "back_edges") == 0) {
-    if (value < 0 || value > (1 << 20)) return set_error(-2, "back_edges must be in [0, 2^20]");
-    s->back_edges = (uint32_t)value;
-    return 0;
-  }
-  if (strcmp(key, "back_wgs") == 0) {
-    if (value < 1 || value > 3) return set_error(-2, "back_wgs must be in [1, 3]");
-    s->back_wgs = (int)value;
-    return 0;
-  }
-
-  return set_error(-2, "unknown knob '%s'", key);
+  return 0;
 }
 
 int kg_snapshot_tune(kg_snapshot* sp, const char* key, int64_t value) {

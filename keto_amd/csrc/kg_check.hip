@@ -980,7 +980,7 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
   // per-launch level events only when asked for (kg_snapshot_tune "level_events"): an event record
   // between back-to-back launches leaves a gap in the stream (round 6: -15 % on the headline with
   // stats on every batch)
-  w->lev_on = stats != nullptr && s->level_events != 0;
+  w->lev_on = stats != nullptr && s->knobs.level_events != 0;
   w->lev_n = 0;
   w->lev_kind = 0;
   w->lev_launches = 0;
@@ -1063,7 +1063,7 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
     const uint32_t nblk = (uint32_t)((n + 255) / 256);
     // kg_snapshot_tune "holder_sig" 0: k_resolve does not see the signatures and reads the holder bitmap
     DevSnap rs = s->ds;
-    if (!s->holder_sig) rs.hsig = nullptr;
+    if (!s->knobs.holder_sig) rs.hsig = nullptr;
     hipLaunchKernelGGL(k_resolve, dim3(nblk), dim3(256), 0, stream, rs, d_q, pq, (uint32_t)n, (uint32_t)n_base, n_extra,
                        global_max_depth, rq, d_out, d_err, gen, use_back ? 2 : 0, ctl, lq,
                        lq_cap);
@@ -1072,14 +1072,14 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
     {
       // ~25 KiB of LDS per workgroup (4 waves: a 256-key visited cache and a 256-entry FIFO each);
       // stream_wgs per CU (default 2: the rest of the LDS serves the other batches in flight)
-      const uint32_t per_cu = s->stream_wgs ? (uint32_t)s->stream_wgs : 2u;
-      const uint32_t ecap = s->stream_ecap ? s->stream_ecap : 0xFFFFFFFFu;
+      const uint32_t per_cu = s->knobs.stream_wgs ? (uint32_t)s->knobs.stream_wgs : 2u;
+      const uint32_t ecap = s->knobs.stream_ecap ? s->knobs.stream_ecap : 0xFFFFFFFFu;
       // >= 8 workgroups: with stream_steal < 8 a wave drains only `ranges` of the 8 per-XCD ranges
       // starting at its label blockIdx & 7, so every label must occur for every range to be drained
       const uint32_t grid =
           std::max<uint32_t>(8u, (uint32_t)std::min<uint64_t>((uint64_t)s->n_cu * per_cu, (n + 31) / 32 + 8));
       hipLaunchKernelGGL((k_stream4<KG_STREAM_VLOG2, KG_STREAM_QC, KG_STREAM_EPL>), dim3(grid), dim3(256), 0, stream, s->ds, LqList{lq, ctl->light8, lq_cap},
-                         ctl->heads, d_out, rq, heavy, &ctl->heavy_count, ctl, ecap, S4_CHUNK, s->stream_steal);
+                         ctl->heads, d_out, rq, heavy, &ctl->heavy_count, ctl, ecap, S4_CHUNK, s->knobs.stream_steal);
     }
     HIPC(hipGetLastError());
     if (stats) HIPC(hipEventRecord(l1, stream));
@@ -1091,9 +1091,9 @@ int check_batch_begin(Snapshot* s, Workspace* w, const kg_query* d_q, size_t n, 
         // one query per wave (~48 KiB LDS per workgroup: 3 per CU); its overflow goes to the grid tier
         // (the workgroup-per-query width k_back<256> between them measured no better and was removed
         // in round 6 with the "back" knob)
-        hipLaunchKernelGGL(k_back<64>, dim3((uint32_t)s->n_cu * s->back_wgs), dim3(256), 0, stream, s->ds, rq, heavy,
+        hipLaunchKernelGGL(k_back<64>, dim3((uint32_t)s->n_cu * s->knobs.back_wgs), dim3(256), 0, stream, s->ds, rq, heavy,
                            &ctl->heavy_count, ctl->bheads[0], d_out, d_err, back2, &ctl->back2_count, ctl,
-                           (uint32_t)s->back_edges);
+                           (uint32_t)s->knobs.back_edges);
         HIPC(hipGetLastError());
         fwd_list = back2;
         fwd_count = &ctl->back2_count;

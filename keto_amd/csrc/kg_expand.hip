@@ -1401,17 +1401,17 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
   ExpandBufs& B = *static_cast<ExpandBufs*>(*bufs);
   B.device = s->device;
   const uint32_t stack_cap = (uint32_t)std::min<int64_t>(0x8000, (int64_t)global + 2);
-  bool gw_on = s->expand_gw != 0;
+  bool gw_on = s->knobs.expand_gw != 0;
   const uint32_t gw_n[2] = {std::max<uint32_t>(1, (uint32_t)s->n_cu / 2), 4};
   const uint32_t grid1 = (uint32_t)s->n_cu * 2, slots1 = grid1 * 4;
   // pass 0 (16-lane walkers, 16 per workgroup) unless expand_skip_lds says otherwise (1: no LDS pass
   // at all, 2: the 64-lane pass takes every root)
-  const bool sub_on = s->expand_skip_lds == 0;
+  const bool sub_on = s->knobs.expand_skip_lds == 0;
   const uint32_t grid0 = (uint32_t)s->n_cu * 2, slots0 = sub_on ? grid0 * (256 / SW) : 0u;
   const uint64_t nn = std::max<uint32_t>(s->ds.n_nodes, 1), words = ((nn + 31) / 32 + 1 + 3) & ~3ull;
   // pass 2: 2 slots per CU, each a visited hash + list of up to 256 Ki nodes (~5 MB a slot, <= 2 GiB;
   // 4 per CU measured the same on C5)
-  const uint64_t cap2 = (std::min<uint64_t>(nn, s->expand_hash_cap) + 3) & ~3ull;
+  const uint64_t cap2 = (std::min<uint64_t>(nn, s->knobs.expand_hash_cap) + 3) & ~3ull;
   uint64_t tsize = 64;
   while (tsize < 2 * cap2 + 128) tsize <<= 1;
   const uint32_t slots2 =
@@ -1479,7 +1479,7 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
                          B.outs, B.arena, B.next, n_chunks,
                          B.stacks + (size_t)(slots1 + slots2 + 1 + gw_n[0] + gw_n[1]) * stack_cap, stack_cap, B.p2 + 4 * n);
     hipLaunchKernelGGL(k_expand_lds, dim3(grid1), dim3(256), 0, stream, s->ds, d_roots, (uint32_t)n, global, B.ctl,
-                       B.outs, B.arena, B.next, n_chunks, B.stacks, stack_cap, B.p2, s->expand_skip_lds == 1 ? 1 : 0,
+                       B.outs, B.arena, B.next, n_chunks, B.stacks, stack_cap, B.p2, s->knobs.expand_skip_lds == 1 ? 1 : 0,
                        sub_on ? (const uint32_t*)(B.p2 + 4 * n) : nullptr);
     // pass-1 overflows: gather-walk small slots -> large slots -> the hash pass (or straight to it)
     uint32_t* q_hash = B.p2;
@@ -1489,7 +1489,7 @@ int expand_batch(Snapshot* s, hipStream_t stream, void** bufs, const kg_set* roo
       ExpFrame* gst = B.stacks + (size_t)(slots1 + slots2 + 1) * stack_cap;
       hipLaunchKernelGGL(k_expand_gw, dim3(gw_n[0] + gw_n[1]), dim3(256), 0, stream, s->ds, d_roots, global, B.ctl,
                          B.outs, B.arena, B.next, n_chunks, gst, stack_cap, B.p2, B.p2 + 2 * n, B.p2 + 3 * n,
-                         (uint32_t)n, gw_n[1], B.gws[0], B.gws[1], (uint64_t)s->expand_gw_wait_us * 100);  // 100 MHz clock
+                         (uint32_t)n, gw_n[1], B.gws[0], B.gws[1], (uint64_t)s->knobs.expand_gw_wait_us * 100);  // 100 MHz clock
       hipLaunchKernelGGL(k_gw_sweep, dim3(1), dim3(256), 0, stream, B.ctl, B.p2 + 2 * n, B.p2 + 3 * n);
       q_hash = B.p2 + 3 * n;
       c_hash = &B.ctl->gb_count;

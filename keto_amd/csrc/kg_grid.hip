@@ -576,7 +576,7 @@ int grid_tier(Snapshot* s, Workspace* w, const RQuery* rq, const uint32_t* qlist
   if (!pin) return set_error(-1, "pinned host buffer");
   uint32_t* hb = (uint32_t*)(pin + 32768);  // the lower half holds the batch's Ctl readback
   const uint64_t full_cap = grid_full_cap(s);
-  const uint64_t small_cap = std::min<uint64_t>(full_cap, s->grid_small_cap ? s->grid_small_cap : 16ull << 20);
+  const uint64_t small_cap = std::min<uint64_t>(full_cap, s->knobs.grid_small_cap ? s->knobs.grid_small_cap : 16ull << 20);
   GridPool* gp = &w->grid;
   std::unique_lock<std::mutex> giant_lk(s->giant_mu, std::defer_lock);
   GridView v;
@@ -594,7 +594,7 @@ int grid_tier(Snapshot* s, Workspace* w, const RQuery* rq, const uint32_t* qlist
     }
     const uint64_t epoch = gp->epoch;
     const uint32_t slot_blocks = (G + 255) / 256;
-    const uint32_t lgrid = (uint32_t)s->n_cu * s->grid_wgs;
+    const uint32_t lgrid = (uint32_t)s->n_cu * s->knobs.grid_wgs;
     // the first round of a batch keeps its counters in the caller's zeroed Ctl (kg_grid.h), later
     // rounds in the pool's own block
     const bool fold = phase == 1 && dsum;

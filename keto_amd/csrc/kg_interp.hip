@@ -457,6 +457,7 @@ __device__ void finish_query(uint32_t qi, int r, uint32_t e, uint8_t* out, uint3
 // 512-node list per wave (6.3 KB; a 512 / 256 variant that fits 8 workgroups per CU measured the
 // same on C3: the extra resident waves were offset by more queries reaching pass 2).
 constexpr int ILDS_VL2 = VIS_LOG2, ILDS_LIST = LIST;
+constexpr int INTERP_WGS = 6;  // k_interp_lds workgroups (4 waves) per CU (6 fit the LDS)
 using ILdsStore = LdsStoreT<ILDS_VL2, ILDS_LIST>;
 __global__ __launch_bounds__(256) void k_interp_lds(DevSnap s, const kg_query* __restrict__ oq,
                                                     const RQuery* __restrict__ rq, const uint32_t* gen_list,
@@ -589,7 +590,7 @@ int launch_general(Snapshot* s, Workspace* w, const kg_query* d_q, const RQuery*
                    const uint32_t* gen_count, InterpCtl* ic, uint8_t* out, uint32_t* err, uint32_t n_queries,
                    hipStream_t stream) {
   if (!s->has_program) return 0;  // without rewrites nothing is ever routed GENERAL
-  const uint32_t grid1 = (uint32_t)s->n_cu * (uint32_t)s->interp_wgs;
+  const uint32_t grid1 = (uint32_t)s->n_cu * (uint32_t)INTERP_WGS;
   const uint32_t slots1 = grid1 * 4;
   const uint64_t nn = std::max<uint32_t>(s->ds.n_nodes, 1);
   const uint64_t words = ((nn + 31) / 32 + 1 + 3) & ~3ull;  // 16-B multiple: clear_bitmap stores uint4
@@ -597,7 +598,7 @@ int launch_general(Snapshot* s, Workspace* w, const kg_query* d_q, const RQuery*
   static_assert((STACK_CAP * sizeof(Frame) + MEMO_CAP * sizeof(MemoEnt)) % 16 == 0, "tables follow the slots 16-B aligned");
   // pass 2: 4 slots per CU (8 measured the same on C3: the pass is tail-bound), each a visited hash
   // + list of cap2 nodes (default 256 Ki: ~3 MB a slot)
-  const uint64_t cap2 = (std::min<uint64_t>(nn, s->interp_cap2 ? s->interp_cap2 : 1ull << 18) + 3) & ~3ull;
+  const uint64_t cap2 = (std::min<uint64_t>(nn, s->knobs.interp_cap2 ? s->knobs.interp_cap2 : 1ull << 18) + 3) & ~3ull;
   uint64_t tsize = 64;
   while (tsize < 2 * cap2 + 128) tsize <<= 1;
   const uint64_t per2 = slot_bytes + (tsize + cap2) * 4;

@@ -1090,14 +1090,14 @@ struct Call {
     HIPC(hipMemcpyAsync(B.h_res.get(), B.d_res.get(), n * sizeof(Res), hipMemcpyDeviceToHost, st));
     if (int rc = w->wait(st, true)) return rc;
     *res = (const Res*)B.h_res.get();
-    O.cap = s->lookup_cap ? s->lookup_cap : std::max<u64>(65536, B.okeys.cap());
+    O.cap = s->knobs.lookup_cap ? s->knobs.lookup_cap : std::max<u64>(65536, B.okeys.cap());
     HIPC(B.okeys.reserve((size_t)O.cap));
     return 0;
   }
 
   // the candidate key list of a call with formula requests; starts at lookup_cap like the output keys
   int want_cand_keys() {
-    K.cap = s->lookup_cap ? s->lookup_cap : std::max<u64>(65536, B.kkeys.cap());
+    K.cap = s->knobs.lookup_cap ? s->knobs.lookup_cap : std::max<u64>(65536, B.kkeys.cap());
     HIPC(B.kkeys.reserve((size_t)K.cap));
     return 0;
   }
@@ -1895,7 +1895,7 @@ void plan_subjects(Call& c, const kg_lookup_subj_set* reqs, const SReq* sr, Subj
 int subject_domain(Call& c, const uint32_t* csub, u64 n_rows, const uint32_t** dom, u64* n_dom) {
   LookupBufs& B = c.B;
   const DevSnap& ds = c.s->ds;
-  const bool bits = ds.hbits && !c.s->lookup_domain_rows;
+  const bool bits = ds.hbits && !c.s->knobs.lookup_domain_rows;
   u64 dcap = std::max<u64>(65536, B.dom.cap());
   for (;;) {
     HIPC(B.dom.reserve((size_t)dcap));
@@ -2015,7 +2015,7 @@ static int lookup_objects_on(Snapshot* s, Lane* L, const kg_lookup* reqs, const 
   c.pg = pages;
   c.mask = mask;
   const LReq* lr = nullptr;
-  const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
+  const bool formula = s->knobs.lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &lr, [&](uint32_t blocks, const kg_lookup* d_req, LReq* d_lr) {
         hipLaunchKernelGGL(k_lk_resolve, dim3(blocks), dim3(256), 0, c.st, s->ds, formula ? s->d_fidx : nullptr,
                            (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, (uint64_t)s->n_check_rows, d_lr);
@@ -2052,7 +2052,7 @@ static int lookup_subjects_on(Snapshot* s, Lane* L, const kg_lookup_subj_set* re
   const uint32_t* csub = ds.crow_off ? ds.crow_subj : ds.row_subj;
   const uint64_t n_rows = s->n_check_rows;
   const SReq* sr = nullptr;
-  const bool formula = s->lookup_formula && s->n_fplans && s->d_fidx;
+  const bool formula = s->knobs.lookup_formula && s->n_fplans && s->d_fidx;
   if (int rc = c.begin(reqs, n, &sr, [&](uint32_t blocks, const kg_lookup_subj_set* d_req, SReq* d_sr) {
         hipLaunchKernelGGL(k_ls_resolve, dim3(blocks), dim3(256), 0, c.st, ds, formula ? s->d_fidx : nullptr,
                            (const FPlan*)s->d_fplans, d_req, (uint32_t)n, c.gmax, d_sr);

@@ -620,8 +620,8 @@ int ms_layout(GridPool* P, uint32_t n, int K, uint32_t G, uint64_t cap, MsView* 
 // Words per mask for this snapshot: the configured width, halved until one group's masks fit an
 // eighth of the budget (0: none fits).
 int ms_words(const Snapshot* s) {
-  for (int K = s->grid_ms_words; K >= 1; K >>= 1)
-    if (ms_group_bytes(s->ds.n_nodes, K) * 8 <= s->grid_ms_bytes) return K;
+  for (int K = s->knobs.grid_ms_words; K >= 1; K >>= 1)
+    if (ms_group_bytes(s->ds.n_nodes, K) * 8 <= s->knobs.grid_ms_bytes) return K;
   return 0;
 }
 
@@ -634,17 +634,17 @@ int ms_rounds(Snapshot* s, Workspace* w, const RQuery* rq, const uint32_t* qlist
   uint32_t* hb = (uint32_t*)(pin + 32768);
   const uint32_t n = s->ds.n_nodes;
   const uint32_t g_max =
-      (uint32_t)std::max<size_t>(1, std::min<size_t>((1u << 20) / Q, s->grid_ms_bytes / ms_group_bytes(n, K)));
-  const uint64_t cap = s->grid_ms_cap ? s->grid_ms_cap : 16ull << 20;  // entries per level buffer
+      (uint32_t)std::max<size_t>(1, std::min<size_t>((1u << 20) / Q, s->knobs.grid_ms_bytes / ms_group_bytes(n, K)));
+  const uint64_t cap = s->knobs.grid_ms_cap ? s->knobs.grid_ms_cap : 16ull << 20;  // entries per level buffer
   GridPool* gp = &w->ms;
   MsView v{};
   uint32_t G = g_max;
-  v.tg_cap = s->grid_ms_tg_cap;
+  v.tg_cap = s->knobs.grid_ms_tg_cap;
   if (int rc = ms_layout(gp, n, K, G, std::min<uint64_t>(cap, (uint64_t)G * n + 1024), &v)) return rc;
   const int levels = std::max(0, global_max_depth - 1);  // level L expands hop L (D - 2 >= L)
   // at least 4 workgroups per CU: an MS-BFS level walks whole hub layers (the per-query grid tier's few
   // edges per level prefer grid_wgs = 2; the heavy-tail point lost 12 % at 2, profiles/r4h2_heavy_knobs_ab.jsonl)
-  const uint32_t lgrid = (uint32_t)s->n_cu * (uint32_t)std::max(4, s->grid_wgs);
+  const uint32_t lgrid = (uint32_t)s->n_cu * (uint32_t)std::max(4, s->knobs.grid_wgs);
   int64_t count = -1;
   bool resume = phase == 2;
   for (uint32_t done = 0; count < 0 || done < (uint64_t)count;) {
@@ -721,7 +721,7 @@ int ms_rounds(Snapshot* s, Workspace* w, const RQuery* rq, const uint32_t* qlist
 // Whether the MS-BFS path serves this snapshot's grid tier (kg_snapshot_tune "grid_ms"): one group's
 // dense masks must fit an eighth of the pool budget, and the holder index must exist.
 bool ms_usable(const Snapshot* s, int global_max_depth) {
-  if (!s->grid_ms || !s->ds.hold || !s->ds.hslots || s->ds.n_nodes == 0 || global_max_depth > MS_HOPS) return false;
+  if (!s->knobs.grid_ms || !s->ds.hold || !s->ds.hslots || s->ds.n_nodes == 0 || global_max_depth > MS_HOPS) return false;
   return ms_words(s) > 0;
 }
 

@@ -486,7 +486,7 @@ int QCall::one(const kg_row_query& x, const QRes& r, uint32_t* take, uint64_t* m
   if (!d.total) return 0;
   if (d.lo + d.total > total && !d.m) return set_error(-1, "query: a row range past the rows");
   const QSel f{r.smode, r.subj, x.after};
-  const u64 cap = std::max<u64>(s->query_cap ? s->query_cap : (1ull << 20), std::min<u64>(x.limit, d.total));
+  const u64 cap = std::max<u64>(s->knobs.query_cap ? s->knobs.query_cap : (1ull << 20), std::min<u64>(x.limit, d.total));
   HIPC(B.ckey.reserve((size_t)cap));
   HIPC(B.cpos.reserve((size_t)cap));
   if (int rc = reset_ctl()) return rc;

@@ -513,6 +513,7 @@ __device__ __forceinline__ uint64_t seg_src(const uint64_t* s_segpre, uint32_t n
 // d_n_in[k] records (clamped to seg_cap) from in[k * seg_cap]; the level walks their concatenation.
 // (The compiler's choice of registers: forcing 6 or 8 waves per SIMD -- round 5's "shard_level_occ"
 // knob -- measured no better, profiles/r5k_level_occupancy_pack_ab.jsonl.)
+constexpr uint32_t SHARD_WGS = 8;  // workgroups per CU of k_shard_level and the other per-record shard kernels
 __global__ __launch_bounds__(256) void k_shard_level(DevSnap s, const kg_frec* __restrict__ in, uint64_t n_bound,
                                                      const uint32_t* d_n_in, kg_frec* out, uint64_t cap, uint32_t* counts, uint8_t* res,
                                                      uint32_t* err, uint64_t* vis, uint64_t vmask,
@@ -1150,7 +1151,7 @@ static int shard_vis_prepare(Snapshot* s, ShardCtx* c, hipStream_t stream, size_
   // per-batch (query, node) table of 2^shard_vis_log2 slots (kg_snapshot_tune "shard_vis",
   // default 2^23 = 64 MiB); an overflow is reported in the flags and the driver grows it
   (void)n;
-  const uint64_t slots = 1ull << s->shard_vis_log2;
+  const uint64_t slots = 1ull << s->knobs.shard_vis_log2;
   if (c->vis_slots != slots) c->vis.reset();
   HIPC(c->vis.reserve(slots));
   c->vis_slots = slots;
@@ -1169,7 +1170,7 @@ static HeavyList heavy_list(ShardCtx* c) {
 
 // Escalation is on for snapshots without a namespace program (errors below the root cannot occur)
 // whose reverse indexes exist, with a non-zero budget.
-bool shard_escalates(const Snapshot* s) { return s->shard_budget && !s->ds.relflags && s->ds.radj; }
+bool shard_escalates(const Snapshot* s) { return s->knobs.shard_budget && !s->ds.relflags && s->ds.radj; }
 
 int shard_seed(Snapshot* s, const kg_query* d_q, size_t n, int32_t gdepth, kg_frec* d_out, size_t cap,
                uint32_t* d_counts, uint8_t* d_res, uint32_t* d_err, hipStream_t stream) {
@@ -1230,12 +1231,12 @@ int shard_level(Snapshot* s, const kg_frec* d_in, size_t n_in, const uint32_t* d
   if (n_in) {
     const HeavyList heavy = heavy_list(c);
     if (!prezeroed) HIPC(hipMemsetAsync(heavy.pk, 0, 8, stream));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_in + 255) / 256, (uint64_t)s->n_cu * s->shard_wgs);
-    const uint32_t budget = shard_escalates(s) && c->qcnt && !c->final ? s->shard_budget : 0u;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_in + 255) / 256, (uint64_t)s->n_cu * SHARD_WGS);
+    const uint32_t budget = shard_escalates(s) && c->qcnt && !c->final ? s->knobs.shard_budget : 0u;
     hipLaunchKernelGGL(k_shard_level, dim3(grid), dim3(256), 0, stream, s->ds, d_in, (uint64_t)n_in, d_n_in, d_out,
                        (uint64_t)cap, d_counts, d_res, d_err, (uint64_t*)c->vis, c->vis_slots - 1,
                        d_done, d_done ? done_words : 0u, heavy, (uint32_t*)c->qcnt,
-                       budget, n_seg, (uint64_t)seg_cap, s->shard_heavy, 1u, 0u);
+                       budget, n_seg, (uint64_t)seg_cap, s->knobs.shard_heavy, 1u, 0u);
     HIPC(hipGetLastError());
     hipLaunchKernelGGL(k_shard_heavy, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, stream, s->ds, heavy, d_out,
                        (uint64_t)cap, d_counts, d_res, d_err, s->shard_n, 1u, nullptr, 0u, nullptr, nullptr);
@@ -1261,8 +1262,8 @@ int shard_levels(Snapshot* s, int levels, kg_frec* d_buf[2], size_t cap, uint32_
   HIPC(c->bits.reserve((size_t)words + 1));
   const HeavyList heavy = heavy_list(c);
   const uint32_t esc = esc_mode == 1 ? ESC_BIT : (esc_mode == 2 ? ESC2_BIT : 0u);
-  const uint32_t budget = shard_escalates(s) && c->qcnt && !c->final ? s->shard_budget : 0u;
-  const uint32_t grid = (uint32_t)std::min<uint64_t>((cap + 255) / 256, (uint64_t)s->n_cu * s->shard_wgs);
+  const uint32_t budget = shard_escalates(s) && c->qcnt && !c->final ? s->knobs.shard_budget : 0u;
+  const uint32_t grid = (uint32_t)std::min<uint64_t>((cap + 255) / 256, (uint64_t)s->n_cu * SHARD_WGS);
   // the levels' records go to SUB per-XCD segments of one buffer, each with its own counter (emit's
   // sub mode): level 0 reads the seed's bucket, every later level the SUB segments of the one before
   const uint32_t SUB = cap >= 8 * 256 ? 8u : 1u;
@@ -1295,7 +1296,7 @@ int shard_levels(Snapshot* s, int levels, kg_frec* d_buf[2], size_t cap, uint32_
     hipLaunchKernelGGL(k_shard_level, dim3(grid), dim3(256), 0, stream, s->ds, d_buf[cur], (uint64_t)cap,
                        seg_in ? sub[cur] : d_counts[cur], d_buf[nx], seg, sub[nx], d_res, d_err, (uint64_t*)c->vis,
                        c->vis_slots - 1, k > 0 && !direct ? (const uint32_t*)c->bits : nullptr, direct ? 0u : w, hk,
-                       (uint32_t*)c->qcnt, budget, seg_in ? SUB : 1u, seg_in ? seg : (uint64_t)0, s->shard_heavy, SUB,
+                       (uint32_t*)c->qcnt, budget, seg_in ? SUB : 1u, seg_in ? seg : (uint64_t)0, s->knobs.shard_heavy, SUB,
                        direct && k > 0 && slots ? 1u : 0u);
     HIPC(hipGetLastError());
     // direct: the level after this one writes sub[cur] (this level's input counters) and pk2[(k+1) & 1]
@@ -1371,9 +1372,9 @@ int shard_back_seed(Snapshot* s, const kg_frec* d_list, size_t m, const uint32_t
   if (!stream) stream = s->stream;
   HIPC(hipMemsetAsync(d_counts, 0, 8, stream));
   if (m && s->ds.radj) {
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((m + 255) / 256, (uint64_t)s->n_cu * s->shard_wgs);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((m + 255) / 256, (uint64_t)s->n_cu * SHARD_WGS);
     hipLaunchKernelGGL(k_shard_back_seed, dim3(grid), dim3(256), 0, stream, s->ds, d_list, (uint64_t)m, d_m, d_out,
-                       (uint64_t)cap, d_counts, n_seg, (uint64_t)seg_cap, s->shard_back_budget);
+                       (uint64_t)cap, d_counts, n_seg, (uint64_t)seg_cap, s->knobs.shard_back_budget);
     HIPC(hipGetLastError());
   }
   return 0;
@@ -1391,11 +1392,11 @@ int shard_back_level(Snapshot* s, const kg_frec* d_in, size_t n_in, const uint32
   if (n_in && s->ds.radj) {
     const HeavyList heavy = heavy_list(c);
     HIPC(hipMemsetAsync(heavy.pk, 0, 8, stream));
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_in + 255) / 256, (uint64_t)s->n_cu * s->shard_wgs);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((n_in + 255) / 256, (uint64_t)s->n_cu * SHARD_WGS);
     hipLaunchKernelGGL(k_shard_back_level, dim3(grid), dim3(256), 0, stream, s->ds, d_in, (uint64_t)n_in, d_n_in, d_out,
                        (uint64_t)cap, d_counts, d_res, d_err, (uint64_t*)c->vis, c->vis_slots - 1, d_done,
                        d_done ? done_words : 0u, heavy, (uint32_t*)c->qcnt,
-                       c->qcnt ? s->shard_back_budget : 0u, n_seg, (uint64_t)seg_cap);
+                       c->qcnt ? s->knobs.shard_back_budget : 0u, n_seg, (uint64_t)seg_cap);
     HIPC(hipGetLastError());
     hipLaunchKernelGGL(k_shard_heavy, dim3((uint32_t)s->n_cu * 4), dim3(256), 0, stream, s->ds, heavy, d_out,
                        (uint64_t)cap, d_counts, d_res, d_err, 1u, 1u, nullptr, 0u, nullptr, nullptr);

@@ -352,7 +352,7 @@ static int comm_setup(Snapshot* s, ShardComm* c) {
   // and every rank has the same node id space (node ids are global: kg_snapshot.hip create_from_tuples)
   const uint64_t nn = s->ds.n_nodes;
   DevBuf<uint64_t> dmeta;  // allocated before the agreement: a rank without it makes every rank skip
-  if (c->world > 1 && !s->ds.remote_meta && s->shard_remote_meta && nn && dmeta.reserve(nn)) (void)hipGetLastError();
+  if (c->world > 1 && !s->ds.remote_meta && s->knobs.shard_remote_meta && nn && dmeta.reserve(nn)) (void)hipGetLastError();
   // a host-memory transport stages the all-reduce through pinned memory: taken now, so a rank that
   // cannot have it makes every rank skip instead of failing alone inside the collective below
   if (dmeta && c->t.host_memory && !pinned_at_least(c, nn * 8)) dmeta.reset();
@@ -404,7 +404,7 @@ static int bind(Snapshot* s, ShardComm* c, hipStream_t st) {
                      s->shard_rank, s->shard_n);
   c->bound = st;
   c->run = st ? st : s->stream;
-  c->bucket = s->shard_bucket0;
+  c->bucket = s->knobs.shard_bucket0;
   c->device = s->device;
   if (int rc = comm_setup(s, c)) return rc;
   std::shared_ptr<ShardComm> old;  // a previous binding of st: destroyed outside the lock, once unused
@@ -602,7 +602,7 @@ int shard_expand(Snapshot* s, const kg_set* roots, size_t n, int32_t gdepth, kg_
   std::lock_guard<std::mutex> lk(c->mu);
   HIPC(hipSetDevice(s->device));
   if (gdepth < 1) gdepth = 5;  // config.schema.json:308-315 default
-  if (c->world == 1 && !s->shard_force_exchange && s->shard_local) {
+  if (c->world == 1 && !s->knobs.shard_force_exchange && s->knobs.shard_local) {
     // one rank holds every row: nothing to gather (local-first, as shard_check); the buffers stay on
     // the comm for the next call (held under c->mu, like every other comm buffer)
     return expand_batch(s, s->stream, &c->xbufs, roots, n, gdepth, out);
@@ -641,7 +641,7 @@ static void drop_buffers(ShardComm* c) {
 // Bucket buffers may take this much (kg_snapshot_tune "shard_max_bytes"; default a quarter of the free
 // HBM, counting what the buffers being replaced hold).
 static uint64_t bucket_byte_cap(const Snapshot* s, const ShardComm* c) {
-  if (s->shard_max_bytes) return s->shard_max_bytes;
+  if (s->knobs.shard_max_bytes) return s->knobs.shard_max_bytes;
   size_t fr = 0, total = 0;
   if (hipMemGetInfo(&fr, &total) != hipSuccess) return ~0ull;
   return (fr + 3 * c->recs * sizeof(kg_frec)) / 4;
@@ -694,9 +694,9 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
   const uint32_t N = (uint32_t)c->world;
   // the exchange protocol runs at N > 1, and at N = 1 when forced (kg_snapshot_tune
   // "shard_force_exchange": the same RCCL calls as N > 1, each rank its own peer)
-  const bool xch = N > 1 || s->shard_force_exchange;
+  const bool xch = N > 1 || s->knobs.shard_force_exchange;
   memset(c->st, 0, sizeof c->st);
-  if (!xch && s->shard_local) {
+  if (!xch && s->knobs.shard_local) {
     // Local-first, one rank: every row is this rank's, so no record of the level protocol would ever
     // leave it -- the batch runs the replica engine's tier chain (k_resolve -> k_stream4 -> k_back ->
     // grid tiers / rewrite interpreter) on the bound stream's workspace instead of level-synchronous
@@ -918,18 +918,18 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
       c->st[13]++;
       continue;
     }
-    if (h[0] || h[1] || s->shard_force_overflow) {  // dropped records somewhere: every rank reruns with more room
-      const bool bucket_over = h[0] || s->shard_force_overflow;
+    if (h[0] || h[1] || s->knobs.shard_force_overflow) {  // dropped records somewhere: every rank reruns with more room
+      const bool bucket_over = h[0] || s->knobs.shard_force_overflow;
       // a run whose visited table overflowed too dropped records for that reason as well, so its
       // bucket counts are lower bounds: only runs without it count against the bucket-rerun bound
       // an exchange downstream of one that dropped records reports a lower bound, so each rerun may
       // fix one more exchange: the default (0) allows max(4, L + 1) reruns
-      const uint32_t max_reruns = s->shard_max_reruns ? s->shard_max_reruns : std::max<uint32_t>(4, xch ? (uint32_t)L + 1 : 0u);
+      const uint32_t max_reruns = s->knobs.shard_max_reruns ? s->knobs.shard_max_reruns : std::max<uint32_t>(4, xch ? (uint32_t)L + 1 : 0u);
       if (bucket_over && !h[1] && run++ >= max_reruns) {
         drop_buffers(c);
         return set_error(KG_ERR_RESOURCE_CODE,
                          "sharded batch still overflows after %u reruns (bucket %zu records per destination, "
-                         "visited table 2^%d keys; kg_snapshot_tune shard_max_reruns)", run - 1, B, s->shard_vis_log2);
+                         "visited table 2^%d keys; kg_snapshot_tune shard_max_reruns)", run - 1, B, s->knobs.shard_vis_log2);
       }
       if (bucket_over) {
         c->st[3]++;
@@ -944,7 +944,7 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
           for (int k = 0; k <= L; k++) {
             const uint64_t need = k < L ? h[8 + (size_t)k] : 0;
             size_t& b = c->lb[(size_t)k];
-            if (need > b || (s->shard_force_overflow && !h[0])) {
+            if (need > b || (s->knobs.shard_force_overflow && !h[0])) {
               b = std::min(top, std::max((size_t)(need * 1.25) + 1024, 2 * b));
               grown = std::max(grown, b);
               after = true;
@@ -962,8 +962,8 @@ int shard_check(Snapshot* s, ShardComm* c, const kg_query* d_q, size_t n, int32_
       if (esc && h[5] > c->bb) c->bb = std::min<size_t>(1ull << 30, std::max((size_t)(h[5] * 1.25) + 1024, 2 * c->bb));
       if (h[1]) {
         c->st[4]++;
-        if (s->shard_vis_log2 >= 34) return set_error(KG_ERR_RESOURCE_CODE, "sharded visited table overflow");
-        s->shard_vis_log2 = std::min(34, s->shard_vis_log2 + 2);
+        if (s->knobs.shard_vis_log2 >= 34) return set_error(KG_ERR_RESOURCE_CODE, "sharded visited table overflow");
+        s->knobs.shard_vis_log2 = std::min(34, s->knobs.shard_vis_log2 + 2);
       }
       continue;
     }

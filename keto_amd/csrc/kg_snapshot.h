@@ -16,6 +16,7 @@
 #include "kg_formula.h"
 #include "kg_grid.h"
 #include "kg_internal.h"
+#include "kg_knobs.h"
 #include "kg_synth.h"
 
 namespace kg {
@@ -319,65 +320,11 @@ struct Snapshot {
   std::mutex comm_mu;
   std::vector<std::shared_ptr<ShardComm>> comms;
   std::atomic<int> n_comms{0};  // comms.size(): the replicated path's lock-free "nothing bound" test
-  int shard_force_exchange = 0;  // kg_snapshot_tune("shard_force_exchange"): one rank runs the N > 1 protocol
-  int shard_local = 1;           // kg_snapshot_tune("shard_local"): one rank runs the replica tier chain
-  int shard_remote_meta = 1;     // kg_snapshot_tune("shard_remote_meta"): bind-time remote child metadata (DevSnap)
-  uint32_t shard_max_reruns = 0;  // kg_snapshot_tune("shard_max_reruns"): overflow reruns per batch (0: max(4, exchanges))
-  uint64_t shard_max_bytes = 0;   // kg_snapshot_tune("shard_max_bytes"): bucket buffers cap (0: 1/4 of free HBM)
-  int shard_force_overflow = 0;   // kg_snapshot_tune("shard_force_overflow"): tests -- every run overflows
+  Knobs knobs;  // kg_snapshot_tune (kg_knobs.h); a snapshot built from another one starts from the defaults
   uint32_t rel_span = 0;          // 1 + the largest relation id of any node (0: not yet computed)
   ProgCopy prog_copy;  // the program the snapshot was built with (the general phase's region snapshots)
   uint32_t* shard_held = nullptr;  // holder bitmap OR-ed over every rank (kg_shard_held), or null
   uint32_t shard_held_n = 0;
-  int shard_vis_log2 = 23;
-  uint32_t shard_bucket0 = 0;  // kg_snapshot_tune("shard_bucket"): first bucket size of new in-library bindings (0: by batch)
-  uint32_t shard_wgs = 8;  // k_shard_level workgroups per CU
-  uint32_t shard_heavy = 64;  // kg_snapshot_tune("shard_heavy"): set rows longer than this go to k_shard_heavy (r3p A/B)
-  uint32_t shard_budget = 0;       // kg_snapshot_tune("shard_budget"): forward set edges per query and rank (0 = off)
-  uint32_t shard_back_budget = 1u << 14;  // kg_snapshot_tune("shard_back_budget"): reverse edges per query and rank
-  uint32_t stream_ecap = 512;  // kg_snapshot_tune("stream_ecap"): stream-tier edge budget per query (0 = none)
-  // kg_snapshot_tune("expand_gw"): pass-1 overflows of kg_expand_batch run gather-then-walk (1) or the
-  // hash pass directly (0); "expand_skip_lds" (tests): 1 = every root skips the LDS passes, 2 = the
-  // 16-lane walkers (pass 0) are skipped and the 64-lane pass takes every root
-  int expand_gw = 1;
-  int expand_skip_lds = 0;
-  uint32_t expand_hash_cap = 1u << 18;  // "expand_hash_cap" (tests): visited sets per hash-pass slot; small values reach the bitmap pass
-  // kg_snapshot_tune("level_events"): batches with stats time every tail-tier level launch with a HIP
-  // event pair (kg_stats tail_ms); off by default -- the records leave gaps between the launches
-  int level_events = 0;
-  // k_expand_gw: longest wait (us) of a large slot for a small slot's hand-on before it gives its ticket up
-  uint32_t expand_gw_wait_us = 100000;
-  int holder_sig = 1;  // kg_snapshot_tune("holder_sig"): k_resolve prunes by the holder signatures (0: the bitmap only; tests, A/B)
-  uint32_t stream_steal = 4;   // kg_snapshot_tune("stream_steal"): XCD ranges a k_stream4 wave dequeues from (1..8)
-  // Occupancy defaults (library-wide, measured with several batches in flight, the way a server keeps
-  // them: C2 and C3 A/Bs in profiles/r2gw_tier_wgs_sweep.jsonl, r2v_occupancy_sweep.jsonl,
-  // r2bw_back_wgs_ab.jsonl; a one-batch-at-a-time caller loses < 5 % with them)
-  // C2 (round 4, profiles/r4w_grid_stream_wgs_ab.jsonl): k_grid_level 2 and k_stream4 2 workgroups per CU
-  // (the LDS a third stream workgroup held now serves the other batches' tail tiers): 7.00 -> 7.20 x 10^9;
-  // C3 keeps 4 / 3 through bench.py
-  int grid_wgs = 2;          // kg_snapshot_tune("grid_wgs"): k_grid_level workgroups per CU
-  int stream_wgs = 2;        // kg_snapshot_tune("stream_wgs"): k_stream4 workgroups per CU (LDS left to other batches)
-  int interp_wgs = 6;        // k_interp_lds workgroups (4 waves) per CU (6 fit the LDS)
-  uint32_t interp_cap2 = 0;  // kg_snapshot_tune("interp_cap2"): pass-2 BFS list cap of the rewrite path (0 = 256 Ki)
-  // k_back workgroups per CU (1..3, LDS allows 3; C3 prefers 1).  3: one wave per query for up to 3 Ki
-  // hand-ons (C2 hands on ~2.2 k per 1 M batch: at 2, ~170 of them waited for a second pass on a
-  // freed wave; 6.3 -> 6.8 x 10^9 checks/s, profiles/r4s_back_wgs_ab.jsonl)
-  int back_wgs = 3;          // kg_snapshot_tune("back_wgs")
-  uint32_t back_edges = 0;   // kg_snapshot_tune("back_edges"): k_back<64>'s reverse-edge budget per query (0 = 2^12)
-  uint64_t grid_small_cap = 0;  // kg_snapshot_tune("grid_cap"): workspace grid-log entries (0 = 16 Mi; tests)
-  int grid_ms = 1;  // kg_snapshot_tune("grid_ms"): grid-tier queries as MS-BFS when the dense masks fit (0: off)
-  size_t grid_ms_bytes = 1ull << 30;  // kg_snapshot_tune("grid_ms_bytes"): MS-BFS mask budget per workspace
-  int grid_ms_words = 8;     // kg_snapshot_tune("grid_ms_words"): 64-bit words per MS-BFS mask (64 queries each)
-  uint32_t grid_ms_tg_cap = 256;  // kg_snapshot_tune("grid_ms_tg_cap"): holders above which MS-BFS probes dset instead
-  uint64_t lookup_cap = 0;  // kg_snapshot_tune("lookup_cap"): initial output entries of a lookup (0 = 64 Ki; tests)
-  // kg_snapshot_tune("lookup_domain_rows") (tests): 1 = kg_lookup_subjects lists its domain from the check
-  // rows even where the holder bitmap exists (what a snapshot without reverse indexes does)
-  int lookup_domain_rows = 0;
-  // kg_snapshot_tune("lookup_formula"): 1 = a lookup on a boolean rewrite takes its candidates from a walk
-  // over the plan's leaves; 0 = from the whole domain (tests, A/B: the answers are the same)
-  int lookup_formula = 1;
-  uint64_t query_cap = 0;  // kg_snapshot_tune("query_cap"): (key, position) pairs a listing sorts directly (0 = 1 Mi; tests)
-  uint64_t grid_ms_cap = 0;  // kg_snapshot_tune("grid_ms_cap"): MS-BFS entries per level buffer (0 = 16 Mi; tests)
   // replicas: the same snapshot on more devices (kg_snapshot_create's device mask); this object is
   // replica 0 and owns the others.  Host-buffer batches and expands are split over all of them.
   std::vector<Snapshot*> peers;
@@ -387,8 +334,7 @@ struct Snapshot {
   std::condition_variable lane_cv;
   std::list<std::vector<Lane*>> lane_sets;     // every set created (list: stable addresses)
   std::vector<std::vector<Lane*>*> lane_free;  // sets not checked out (LIFO: the warmest first)
-  size_t lane_cap = 32;                        // kg_snapshot_tune("max_lanes"): concurrent host-buffer calls
-  std::vector<Lane*>* lanes_acquire();         // a free lane set (created up to lane_cap; waits at the cap)
+  std::vector<Lane*>* lanes_acquire();         // a free lane set (created up to knobs.lane_cap; waits at the cap)
   void lanes_release(std::vector<Lane*>* v);
   std::atomic<uint64_t> rr_next{0};      // replica rotation of batches smaller than one chunk per replica
   // The grid tier's full-size pool (a log that holds every node): shared by the workspaces, used

@@ -442,7 +442,7 @@ int Lane::reserve_packed(size_t n) {
 
 std::vector<Lane*>* Snapshot::lanes_acquire() {
   std::unique_lock<std::mutex> lk(lane_mu);
-  lane_cv.wait(lk, [&] { return !lane_free.empty() || lane_sets.size() < lane_cap; });
+  lane_cv.wait(lk, [&] { return !lane_free.empty() || lane_sets.size() < knobs.lane_cap; });
   if (!lane_free.empty()) {
     std::vector<Lane*>* v = lane_free.back();
     lane_free.pop_back();

@@ -5,7 +5,6 @@ handlers over the host-mode persister (a restatement of the two REST delete case
 internal/relationtuple/transact_server_test.go, their inputs in tests/golden/transact_server_cases.json)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -35,18 +34,12 @@ def test_delete_symbols_exported():
     assert "relationtuples.go:146-162,187-201" in hdr  # the reference lines, as the other entries name theirs
 
 
-def test_delete_struct_layout_matches_header(tmp_path):
+def test_delete_struct_layout_matches_header():
+    from header_probe import probe
     from keto_amd import _lib
-    src = tmp_path / "sz.c"
     fields = ("matched", "keys", "n_queries", "n_deleted", "rows_scanned", "kernel_ms", "pinned")
-    offs = [f"offsetof(kg_delete_buf, {f})" for f in fields]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { size_t v[] = {sizeof(kg_delete_buf), KG_DELETE_MAX_QUERIES, KG_DELETE_KEYS, '
-                   + ", ".join(offs) + '};\n'
-                   '  for (size_t i = 0; i < sizeof v / sizeof *v; i++) printf("%zu ", v[i]);\n  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_delete_buf)", "KG_DELETE_MAX_QUERIES", "KG_DELETE_KEYS"] +
+                [f"offsetof(kg_delete_buf, {f})" for f in fields])
     B = _lib.kg_delete_buf
     want = [C.sizeof(B), _lib.KG_DELETE_MAX_QUERIES, _lib.KG_DELETE_KEYS] + [getattr(B, f).offset for f in fields]
     assert got == want

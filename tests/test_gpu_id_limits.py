@@ -549,24 +549,47 @@ def test_apply_brings_the_extremes(program):
 KNOB_DEFAULTS = {
     "stream_ecap": 512, "stream_steal": 4, "stream_wgs": 2, "back_wgs": 3, "grid_wgs": 2, "back_edges": 0,
     "interp_cap2": 0, "grid_reserve": 0, "grid_cap": 0, "max_lanes": 32, "grid_ms": 1, "grid_ms_words": 8,
-    "grid_ms_bytes": 1 << 30, "grid_ms_tg_cap": 256, "grid_ms_cap": 0, "level_events": 0, "expand_gw": 1,
+    "grid_ms_bytes": 1 << 30, "grid_ms_tg_cap": 256, "grid_ms_cap": 0, "level_events": 0, "holder_sig": 1, "expand_gw": 1,
     "expand_gw_wait_us": 100000, "expand_skip_lds": 0, "expand_hash_cap": 1 << 18, "lookup_cap": 0,
     "lookup_domain_rows": 0, "lookup_formula": 1, "query_cap": 0, "shard_vis": 23, "shard_heavy": 64,
     "shard_budget": 0, "shard_back_budget": 1 << 14, "shard_bucket": 0, "shard_local": 1, "shard_force_exchange": 0,
     "shard_remote_meta": 1, "shard_max_reruns": 0, "shard_max_bytes": 0, "shard_force_overflow": 0,
 }
+# the range the header's comment gives each key (None: no bound on that side; "grid_reserve" takes any value)
+KNOB_RANGES = {
+    "stream_ecap": (0, 2 ** 32 - 1), "stream_steal": (1, 8), "stream_wgs": (0, 8), "back_wgs": (1, 3), "grid_wgs": (1, 64),
+    "back_edges": (0, 2 ** 20), "interp_cap2": (0, 4194304), "grid_reserve": (None, None), "grid_cap": (0, 2 ** 34),
+    "max_lanes": (1, 1024), "grid_ms": (0, 1), "grid_ms_words": (1, 16), "grid_ms_bytes": (2 ** 20, 2 ** 40),
+    "grid_ms_tg_cap": (0, 2 ** 31 - 1), "grid_ms_cap": (0, 2 ** 28), "level_events": (0, 1), "holder_sig": (0, 1),
+    "expand_gw": (0, 1), "expand_gw_wait_us": (0, 10 ** 7), "expand_skip_lds": (0, 2), "expand_hash_cap": (4, 2 ** 18),
+    "lookup_cap": (0, 2 ** 32), "lookup_domain_rows": (0, 1), "lookup_formula": (0, 1), "query_cap": (0, 2 ** 32),
+    "shard_vis": (10, 34), "shard_heavy": (0, 2 ** 32 - 1), "shard_budget": (0, 2 ** 32 - 1),
+    "shard_back_budget": (0, 2 ** 32 - 1), "shard_bucket": (0, 2 ** 26), "shard_local": (0, 1),
+    "shard_force_exchange": (0, 1), "shard_remote_meta": (0, 1), "shard_max_reruns": (0, 64),
+    "shard_max_bytes": (0, None), "shard_force_overflow": (0, 1),
+}
 REMOVED_KNOBS = ["back", "resolve_unheld", "device_sync", "host_sync", "stream_chunk", "interp_wgs", "grid_bidir",
-                 "shard_wgs", "shard_vis_mode", "shard_pack"]
+                 "shard_wgs", "shard_vis_mode", "shard_pack", "shard_level_occ"]
 
 
 def test_knob_list_of_the_header():
     """Every key the kg_snapshot_tune comment of include/ketogpu.h names is accepted at its documented default;
-    an unknown key and every key removed since are refused with -2 and "unknown knob"."""
+    the values just outside its documented range are refused with -2 and an error that names the key; an unknown
+    key and every key removed since are refused with -2 and "unknown knob".  Checks answer as before afterwards."""
     t6 = np.asarray([[0, i, 1, SUBJECT_ID, 20 + i, 0] for i in range(10)], np.uint32)
     snap = Snapshot(t6, sp.SimpleNamespace(n_namespaces=1, n_relations=2, wildcard_rel=0), None)
     L = _lib.load()
+    assert set(KNOB_RANGES) == set(KNOB_DEFAULTS)
     for key, value in KNOB_DEFAULTS.items():
         assert L.kg_snapshot_tune(snap.handle, key.encode(), value) == 0, (key, _lib.last_error())
+    for key, (lo, hi) in KNOB_RANGES.items():
+        outside = ([] if lo is None else [lo - 1]) + ([] if hi is None else [hi + 1])
+        if key == "grid_ms_words":
+            outside += [3, 32]
+        for value in outside:
+            assert L.kg_snapshot_tune(snap.handle, key.encode(), value) == -2, (key, value)
+            assert key in _lib.last_error() and "unknown knob" not in _lib.last_error(), (key, value, _lib.last_error())
+        assert L.kg_snapshot_tune(snap.handle, key.encode(), KNOB_DEFAULTS[key]) == 0, (key, _lib.last_error())
     for key in ["no_such_knob"] + REMOVED_KNOBS:
         assert L.kg_snapshot_tune(snap.handle, key.encode(), 0) == -2, key
         assert "unknown knob" in _lib.last_error(), key

@@ -96,6 +96,48 @@ def test_library_exports_every_declared_symbol():
     assert L.kg_version().startswith(b"ketogpu")
 
 
+def test_binding_table_has_the_header_parameter_counts():
+    """Every entry of keto_amd._lib.BINDINGS lists as many argtypes as the function's declaration in
+    include/ketogpu.h has parameters ((void) and () count as none)."""
+    from keto_amd import _lib
+    with open(os.path.join(ROOT, "include", "ketogpu.h")) as f:
+        code = re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+    decls = re.findall(r"\b(kg_[a-z_]+)\s*\(([^()]*)\)\s*;", code)  # (a static inline helper has a body, not a `;`)
+    counts = {}
+    for name, params in decls:
+        assert name not in counts, name
+        params = params.strip()
+        counts[name] = 0 if params in ("", "void") else len(params.split(","))
+    assert set(counts) == set(_lib.BINDINGS), set(counts) ^ set(_lib.BINDINGS)
+    got = {name: len(argtypes) for name, (_, argtypes) in _lib.BINDINGS.items()}
+    assert got == counts, {n: (got[n], counts[n]) for n in got if got[n] != counts[n]}
+    assert counts["kg_version"] == 0 and counts["kg_shard_level_seg"] == 13  # the parse itself
+
+
+def test_every_ctypes_struct_has_the_header_layout():
+    """Size and every field offset of each ctypes.Structure of keto_amd._lib equal the header's struct of the
+    same name (one compile)."""
+    from header_probe import probe
+    from keto_amd import _lib
+    c_member = {("kg_lookup_page", "from_"): "from"}  # a Python keyword; every other field has the member's name
+    structs = sorted((n, t) for n, t in vars(_lib).items()
+                     if isinstance(t, type) and issubclass(t, ctypes.Structure) and t is not ctypes.Structure)
+    names = [n for n, _ in structs]
+    for old in ("kg_stats", "kg_tree_buf", "kg_tree_node", "kg_synth_params", "kg_rewrite_prog", "kg_dict", "kg_rw_node",
+                "kg_check_node", "kg_shard_transport", "kg_batcher_stats_t", "kg_lookup_mask_buf"):
+        assert old in names, old
+    exprs, want = [], []
+    for name, t in structs:
+        assert t.__name__ == name
+        exprs.append(f"sizeof({name})")
+        want.append(ctypes.sizeof(t))
+        for field, _ in t._fields_:
+            exprs.append(f"offsetof({name}, {c_member.get((name, field), field)})")
+            want.append(getattr(t, field).offset)
+    got = probe(exprs)
+    assert got == want, [(e, g, w) for e, g, w in zip(exprs, got, want) if g != w]
+
+
 def test_library_reports_errors_without_gpu():
     from keto_amd import _lib
     L = _lib.load()

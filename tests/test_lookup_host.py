@@ -2,12 +2,8 @@
 fail before a device is touched, the ABI struct layout against the header, and the handler's request
 decoding."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_lookup_symbols_exported():
@@ -31,16 +27,11 @@ def test_lookup_null_arguments():
     L.kg_lookup_free(C.byref(buf))  # an empty buffer: nothing to return
 
 
-def test_lookup_struct_sizes_match_header(tmp_path):
+def test_lookup_struct_sizes_match_header():
+    from header_probe import probe
     from keto_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(kg_lookup), sizeof(kg_lookup_buf),\n'
-                   '  offsetof(kg_lookup_buf, n_reqs), offsetof(kg_lookup_buf, kernel_ms), offsetof(kg_lookup_buf, pinned));\n'
-                   '  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_lookup)", "sizeof(kg_lookup_buf)", "offsetof(kg_lookup_buf, n_reqs)",
+                 "offsetof(kg_lookup_buf, kernel_ms)", "offsetof(kg_lookup_buf, pinned)"])
     B = _lib.kg_lookup_buf
     assert got == [24, C.sizeof(B), B.n_reqs.offset, B.kernel_ms.offset, B.pinned.offset]
 

@@ -2,29 +2,22 @@
 checks the C ABI makes before it touches a snapshot, and the handlers' order=id page parsing."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from header_probe import probe
 from keto_amd import _lib
 from keto_amd.handlers import HandlerError, ListObjectsHandler, ListSubjectsHandler, parse_id_page
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_page_struct_layout_matches_header(tmp_path):
+def test_page_struct_layout_matches_header():
     fields_p = ("list", "next", "rounds", "pinned")
-    src = tmp_path / "sz.c"
-    offs = [f"offsetof(kg_lookup_pages, {f})" for f in fields_p] + ["offsetof(kg_lookup_page, from)",
-                                                                    "offsetof(kg_lookup_page, limit)"]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { size_t v[] = {sizeof(kg_lookup_page), sizeof(kg_lookup_pages), sizeof(kg_lookup_buf),\n'
-                   '  KG_LOOKUP_END, ' + ", ".join(offs) + '};\n'
-                   '  for (size_t i = 0; i < sizeof v / sizeof *v; i++) printf("%zu ", v[i]);\n  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_lookup_page)", "sizeof(kg_lookup_pages)", "sizeof(kg_lookup_buf)", "KG_LOOKUP_END"] +
+                [f"offsetof(kg_lookup_pages, {f})" for f in fields_p] +
+                ["offsetof(kg_lookup_page, from)", "offsetof(kg_lookup_page, limit)"])
     P, S = _lib.kg_lookup_page, _lib.kg_lookup_pages
     want = [C.sizeof(P), C.sizeof(S), C.sizeof(_lib.kg_lookup_buf), _lib.KG_LOOKUP_END] + \
         [getattr(S, f).offset for f in fields_p] + [P.from_.offset, P.limit.offset]

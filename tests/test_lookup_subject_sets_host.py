@@ -2,12 +2,8 @@
 exports, argument checks that fail before a device is touched, the ABI struct layout against the header, and
 the handler's decoding of the subject-set filter."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_symbols_exported():
@@ -43,20 +39,14 @@ def test_null_arguments():
     L.kg_lookup_pages_free(C.byref(out))
 
 
-def test_struct_layout_matches_header(tmp_path):
+def test_struct_layout_matches_header():
+    from header_probe import probe
     from keto_amd import _lib
     S = _lib.kg_lookup_subj_set
     fields = [f for f, _ in S._fields_]
     assert fields == ["ns", "obj", "rel", "sns", "srel", "max_depth"]
-    src = tmp_path / "sz.c"
-    offs = ", ".join(f"offsetof(kg_lookup_subj_set, {f})" for f in fields)
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { size_t v[] = {sizeof(kg_lookup_subj_set), sizeof(kg_lookup_buf), sizeof(kg_lookup_pages),\n'
-                   f'  KG_SUBJECT_ID, {offs}}};\n'
-                   '  for (size_t i = 0; i < sizeof v / sizeof *v; i++) printf("%zu ", v[i]);\n  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_lookup_subj_set)", "sizeof(kg_lookup_buf)", "sizeof(kg_lookup_pages)", "KG_SUBJECT_ID"] +
+                [f"offsetof(kg_lookup_subj_set, {f})" for f in fields])
     assert C.sizeof(S) == 24
     assert got == [24, C.sizeof(_lib.kg_lookup_buf), C.sizeof(_lib.kg_lookup_pages), _lib.KG_SUBJECT_ID] + \
         [getattr(S, f).offset for f in fields]

@@ -1,12 +1,8 @@
 """Subject lookup (kg_lookup_subjects), the parts that need no GPU: the export, argument checks that fail
 before a device is touched, the ABI struct layout against the header, and the handler's request decoding."""
 import ctypes as C
-import os
-import subprocess
 
 import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_lookup_subjects_symbol_exported():
@@ -28,17 +24,12 @@ def test_lookup_subjects_null_arguments():
     L.kg_lookup_free(C.byref(buf))  # an empty buffer: nothing to return
 
 
-def test_lookup_subjects_struct_sizes_match_header(tmp_path):
+def test_lookup_subjects_struct_sizes_match_header():
+    from header_probe import probe
     from keto_amd import _lib
-    src = tmp_path / "sz.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { printf("%zu %zu %zu %zu %zu %zu\\n", sizeof(kg_lookup_subj), sizeof(kg_lookup_buf),\n'
-                   '  offsetof(kg_lookup_subj, rel), offsetof(kg_lookup_subj, max_depth),\n'
-                   '  offsetof(kg_lookup_buf, n_reqs), offsetof(kg_lookup_buf, pinned));\n'
-                   '  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_lookup_subj)", "sizeof(kg_lookup_buf)", "offsetof(kg_lookup_subj, rel)",
+                 "offsetof(kg_lookup_subj, max_depth)", "offsetof(kg_lookup_buf, n_reqs)",
+                 "offsetof(kg_lookup_buf, pinned)"])
     B = _lib.kg_lookup_buf
     assert C.sizeof(B) == 104  # 4 pointers, 7 counters, kernel_ms, pinned: as before this call existed
     assert got == [16, C.sizeof(B), 8, 12, B.n_reqs.offset, B.pinned.offset]

@@ -5,7 +5,6 @@ ABI struct layout against the header, and the exports."""
 import ctypes as C
 import json
 import os
-import subprocess
 import uuid
 
 import pytest
@@ -147,20 +146,14 @@ def test_device_reads_is_off_by_default_and_host_reads_build_no_snapshot():
     assert p._snap is None and p.rebuilds == 0  # the host path never touches the device
 
 
-def test_query_struct_layout_matches_header(tmp_path):
+def test_query_struct_layout_matches_header():
+    from header_probe import probe
     from keto_amd import _lib
-    src = tmp_path / "sz.c"
     fields_q = ("mask", "t", "after", "limit")
     fields_b = ("req_off", "rows", "keys", "next", "matched", "n_reqs", "n_rows", "rows_scanned", "passes", "kernel_ms",
                 "pinned")
-    offs = [f"offsetof(kg_row_query, {f})" for f in fields_q] + [f"offsetof(kg_query_buf, {f})" for f in fields_b]
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "ketogpu.h"\n'
-                   'int main(void) { size_t v[] = {sizeof(kg_row_query), sizeof(kg_query_buf), KG_Q_NS, KG_Q_OBJ, KG_Q_REL,\n'
-                   '  KG_Q_SUBJECT, ' + ", ".join(offs) + '};\n'
-                   '  for (size_t i = 0; i < sizeof v / sizeof *v; i++) printf("%zu ", v[i]);\n  return 0; }\n')
-    exe = tmp_path / "sz"
-    subprocess.run(["gcc", "-O1", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
+    got = probe(["sizeof(kg_row_query)", "sizeof(kg_query_buf)", "KG_Q_NS", "KG_Q_OBJ", "KG_Q_REL", "KG_Q_SUBJECT"] +
+                [f"offsetof(kg_row_query, {f})" for f in fields_q] + [f"offsetof(kg_query_buf, {f})" for f in fields_b])
     Q, B = _lib.kg_row_query, _lib.kg_query_buf
     want = [C.sizeof(Q), C.sizeof(B), _lib.KG_Q_NS, _lib.KG_Q_OBJ, _lib.KG_Q_REL, _lib.KG_Q_SUBJECT] + \
         [getattr(Q, f).offset for f in fields_q] + [getattr(B, f).offset for f in fields_b]
